@@ -5,12 +5,21 @@ experiments/timing.py (inputs resident on the device, wall clock around the whol
 
   python bench.py [--gpus N --steps K --warmup W] [--batch B] [--height 384 --width 768]
                   [--fusion bayes|dirichlet|joint] [--dtype bf16|fp8] [--mode infer|train]
-                  [--no-cpu-baseline] [--no-accuracy] [--no-extra]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-accuracy] [--no-extra]]
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU); images are
 independent, so ranks shard the batch with no data-path collective ("weak" scaling) and only the
-timing is reduced (MAX over ranks).  Rank 0 prints ONE JSON line:
+timing is reduced (MAX over ranks).  Rank 0 prints ONE JSON line.
 
-  metric / value / roofline / cpu_baseline   the headline workload (contract of the driver)
+A plain run sets up, warms up (W steps, a hipGraph capture, about a second of untimed steps for the
+clocks), times exactly K steps as one block, writes what the last timed step computed if
+--dump-outputs is given (DIR/<name>.npy, float32 / float64, at most 64 MB) and prints the line:
+
+  metric / value / unit / higher_is_better / dtype / ms_per_step   the headline workload
+
+--full adds everything else, each part a run of its own after the headline:
+
+  roofline     the per-kernel pass (HIP events around every conv launch, experts serialised on one stream)
+  cpu_baseline the fp32 PyTorch-CPU oracle on this host's cores
   accuracy     mean IoU of the HIP bf16 and fp8 paths against the fp32 oracle on TRAINED experts (N = 1)
   extra        the other BASELINE.json configurations, each with its own roofline fraction: the reference's
                timing.py protocol (batch 1, tf.ones input, label map fetched to the host), 1024x512 Bayes,
@@ -204,18 +213,21 @@ def fence(device, world, dist):
         torch.cuda.synchronize(device)
 
 
-def timed_blocks(step, steps, device, world, dist, min_seconds):
+def timed_blocks(step, steps, device, world, dist, min_seconds, last=None):
     """The timed region, made robust: blocks of EXACTLY `steps` steps, each bracketed by barrier + synchronize on both
     sides and reduced to the MAX over ranks, repeated until `min_seconds` of timed work have accumulated (a single block
-    of 20 steps is 0.1 s, and box / clock state moved that by +-5 %).  Returns the list of block times (identical on every
-    rank: the loop exit depends only on all-reduced numbers)."""
+    of 20 steps is 0.1 s, and box / clock state moved that by +-5 %; min_seconds=0: exactly one block).  Returns the list
+    of block times (identical on every rank: the loop exit depends only on all-reduced numbers).  last: a list that
+    receives what the final step returned."""
     times = []
     while True:
         fence(device, world, dist)
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            out = step()
         fence(device, world, dist)
+        if last is not None and steps > 0:
+            last[:] = [out]
         dt = time.perf_counter() - t0
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device=device)
@@ -226,6 +238,27 @@ def timed_blocks(step, steps, device, world, dist, min_seconds):
             return times
 
 
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs in all, .npy headers included
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: {name: host array} -> directory/<name>.npy in float32 (float64 stays float64).  Over DUMP_BYTES in
+    all, every array is cut to the same fixed sample fraction: evenly spaced elements of its flattened form from an offset
+    drawn with a fixed seed, so that two runs with the same arguments write the same elements."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    budget = DUMP_BYTES - 1024 * len(arrays)
+    for i, (name, v) in enumerate(sorted(arrays.items())):
+        if total > budget:
+            flat = v.reshape(-1)
+            keep = max(1, int(flat.size * (budget / total)) - 1)
+            stride = -(-flat.size // keep)
+            offset = int(np.random.default_rng(i).integers(0, stride))
+            v = flat[offset::stride]
+        np.save(os.path.join(directory, name + '.npy'), v)
+
+
 def block_stats(times, steps):
     med = float(np.median(times))
     return {'ms_per_step': round(med / steps * 1e3, 4), 'ms_per_step_min': round(min(times) / steps * 1e3, 4),
@@ -234,9 +267,10 @@ def block_stats(times, steps):
 
 
 def measure_inference(net, batch, device, steps, warmup, graph=True, serial=None, world=1, dist=None, fetch=False,
-                      min_seconds=2.0):
-    """Timed region + per-kernel roofline pass of one inference configuration.  Returns (block times of the timed region
-    (max over ranks), [per-iteration seconds] if fetch, conv profile list, block times of the serialised pass)."""
+                      min_seconds=2.0, profile=True, last=None):
+    """Timed region + (profile=True) per-kernel roofline pass of one inference configuration.  Returns (block times of the
+    timed region (max over ranks), [per-iteration seconds] if fetch, conv profile list, block times of the serialised
+    pass; the last two empty without the pass).  last: a list that receives the final timed step's label map."""
     from modular_semantic_segmentation_amd import ops
     # serial: True = the experts back to back on one stream, False = side by side on two, None = the model's own choice
     # (basic_fusion_model.expert_streams: two streams while one expert's launches leave CUs idle)
@@ -302,7 +336,11 @@ def measure_inference(net, batch, device, steps, warmup, graph=True, serial=None
             per_iter.append(time.perf_counter() - ts)
         times = timed_blocks(fstep, steps, device, world, dist, min_seconds)
     else:
-        times = timed_blocks(step, steps, device, world, dist, min_seconds)
+        times = timed_blocks(step, steps, device, world, dist, min_seconds, last=last)
+    if last:
+        last[0] = last[0].cpu()          # (before anything else runs on the buffers the step wrote)
+    if not profile:
+        return times, per_iter, [], []
 
     # Per-kernel roofline pass: the same steps with the two experts serialised on one stream, so that a HIP-event
     # pair around a conv launch (recorded on the launch stream) times that kernel alone (in the timed region above
@@ -642,11 +680,12 @@ def make_trainer_net(args, device, expert, joint, batch, batch_norm=None):
 
 
 def measure_training(args, device, world, rank, dist, batch, steps, warmup, expert='fcn', joint=False, h=None, w=None,
-                     batch_norm=None):
+                     batch_norm=None, min_seconds=1.0, last=None):
     """Data-parallel expert training: every rank differentiates its own images, gradients are all-reduced in buckets on
-    a side stream during backward (RCCL over xGMI).  Returns a record with images/s, the roofline of the MFMA convs
-    (forward + data gradient + filter gradient FLOPs over their summed HIP-event times) and, for N > 1, the exposed
-    all-reduce time (step time minus the same step with the reducer stubbed out)."""
+    a side stream during backward (RCCL over xGMI).  Returns a record with images/s, with --full the roofline of the MFMA
+    convs (forward + data gradient + filter gradient FLOPs over their summed HIP-event times) and, for N > 1, the exposed
+    all-reduce time (step time minus the same step with the reducer stubbed out).  last: a dict that receives the final
+    timed step's loss and parameters (host arrays)."""
     from modular_semantic_segmentation_amd import ops
     h, w = h or args.height, w or args.width
     gen = torch.Generator(device='cpu').manual_seed(99 + rank)
@@ -656,16 +695,26 @@ def measure_training(args, device, world, rank, dist, batch, steps, warmup, expe
         data['depth'] = torch.randint(0, 65536, (batch, h, w, 1), generator=gen).float().to(device)
     net = make_trainer_net(args, device, expert, joint, batch, batch_norm)
 
-    def timed(n, min_seconds=1.0):
+    def timed(n, min_seconds):
         return timed_blocks(lambda: net._train_batch(data), n, device, world, dist, min_seconds)
 
     for _ in range(warmup):
         net._train_batch(data)
-    times = timed(steps)
+    times = timed(steps, min_seconds)
+    if last is not None:
+        # what the caller of the step holds afterwards: the last step's loss and the updated parameters
+        last['loss'] = np.atleast_1d(net.loss.detach().cpu().numpy()).astype(np.float64)
+        last['params'] = net.trainer.param.detach().cpu().numpy()
     dt = float(np.median(times))
     rec = {'value': round(batch * world * steps / dt, 2), 'unit': 'images/s', 'images_per_gpu_per_step': batch,
            'n_gpus': world}
     rec.update(block_stats(times, steps))
+    flops = 3.0 * conv_flops_per_image(h, w, 3) + (3.0 * conv_flops_per_image(h, w, 1) if joint else 0.0)
+    if expert == 'adapnet':
+        flops = 3.0 * adapnet_flops_per_image(h, w, 3)
+    rec['conv_tflops_end_to_end'] = round(batch * world * steps * flops / dt / 1e12, 2)
+    if not getattr(args, 'full', False):
+        return rec
     if world > 1:
         # the same steps without the collective: what the all-reduce costs beyond what backward hides.  The replicas
         # drift apart while the reducer is off, so rank 0's parameters and optimizer slots are broadcast again afterwards.
@@ -717,17 +766,17 @@ def measure_training(args, device, world, rank, dist, batch, steps, warmup, expe
                            'by_pass_tflops': {k: round(v[0] / v[1] / 1e12, 1) for k, v in by.items() if v[1] > 0},
                            'measured': 'HIP events per launch, every kernel on ONE stream (the step itself runs the filter '
                                        'gradients on a second stream)'}
-    flops = 3.0 * conv_flops_per_image(h, w, 3) + (3.0 * conv_flops_per_image(h, w, 1) if joint else 0.0)
-    if expert == 'adapnet':
-        flops = 3.0 * adapnet_flops_per_image(h, w, 3)
-    rec['conv_tflops_end_to_end'] = round(batch * world * steps * flops / dt / 1e12, 2)
     return rec
 
 
 def bench_train(args, device, world, rank, dist):
     joint = args.fusion == 'joint' and args.expert == 'fcn'
     adap = args.expert == 'adapnet'
-    rec = measure_training(args, device, world, rank, dist, args.batch, args.steps, args.warmup, args.expert, joint)
+    last = {} if args.dump_outputs else None
+    rec = measure_training(args, device, world, rank, dist, args.batch, args.steps, args.warmup, args.expert, joint,
+                           min_seconds=args.min_seconds, last=last)
+    if rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last)
     if rank == 0:
         metric = 'images/sec, SimpleFCN RGB expert training step (fwd + bwd + Adam%s) at %dx%d' % (
             ', batch norm' if args.batch_norm else '', args.width, args.height)
@@ -746,10 +795,11 @@ def bench_train(args, device, world, rank, dist):
                'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
                'config': {'workload': workload, 'images_per_gpu_per_step': args.batch, 'global_batch': args.batch * world,
                           'parallelism': 'dp%d, bucketed gradient all-reduce overlapped with backward' % world},
-               'conv_tflops_end_to_end': rec['conv_tflops_end_to_end'], 'roofline': rec.get('roofline'),
-               'cpu_baseline': None,
+               'conv_tflops_end_to_end': rec['conv_tflops_end_to_end'], 'cpu_baseline': None,
                'cpu_baseline_note': 'training has no CPU leg: the oracle differentiates one 64x96 image in seconds (tests), a '
                                     '768x384 step would take minutes; the inference line carries the CPU baseline'}
+        if args.full:
+            out['roofline'] = rec.get('roofline')
         for k in ('ms_per_step_without_allreduce', 'allreduce_ms_exposed', 'gradient_bytes_per_step'):
             if k in rec:
                 out[k] = rec[k]
@@ -758,15 +808,58 @@ def bench_train(args, device, world, rank, dist):
         dist.destroy_process_group()
 
 
+def roofline_records(args, prof, times_serial, flops_img, rank):
+    """--full: the roofline records of the headline configuration from its per-kernel pass."""
+    dt_serial = float(np.median(times_serial))
+    if args.layer_profile and rank == 0:
+        # per-launch-slot breakdown (launch order repeats every step): flops, mean time, TFLOP/s
+        per = len(prof) // max(args.steps * len(times_serial), 1)
+        for i in range(per):
+            evs = prof[i::per]
+            ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in evs) / len(evs)
+            print('  conv launch %2d %s %7.1f GF %8.1f us %7.0f TF/s' % (i, evs[0][0], evs[0][1] / 1e9, ms * 1e3,
+                                                                      evs[0][1] / ms / 1e9), file=sys.stderr)
+    # dominant kernel: the 3x3 implicit-GEMM MFMA conv (fp8: the launches on e4m3 operands, against the fp8 peak)
+    pair = both = None
+    if args.dtype == 'fp8':
+        roofline = roofline_of(prof, ('k3f8',), PEAK_TFLOPS['fp8'],
+                               'conv_f8_dma_kernel (v_mfma_scale_f32_32x32x64_f8f6f4, 3x3 launches on e4m3 operands; conv_mfma_kernel<F8> where a map does not tile in 16x32)',
+                               times_serial, args.steps)
+    else:
+        roofline = roofline_of(prof, ('k3',), PEAK_TFLOPS['bf16'],
+                               'conv_dma4_kernel / conv_dma5_kernel (the 3x3 implicit-GEMM MFMA conv: every launch of conv2_1 .. '
+                               'conv5_3; conv_dma_kernel / conv_mfma_kernel on shapes that do not tile)', times_serial,
+                               args.steps, traffic=committed_traffic(args.batch, args.height, args.width))
+        # conv1_1 + conv1_2 run as ONE kernel (conv_first_fused.hip): reported beside the dominant kernel, with the algorithmic
+        # FLOPs of both layers against the whole kernel's time, and both together so that nothing is left out
+        pair = roofline_of(prof, ('k3pair',), PEAK_TFLOPS['bf16'], 'conv_first_pair_kernel (conv1_1 + conv1_2 + pool1 fused; '
+                           'algorithmic FLOPs of both layers)', times_serial, args.steps)
+        both = roofline_of(prof, ('k3', 'k3pair'), PEAK_TFLOPS['bf16'], 'all of the above', times_serial, args.steps)
+    if args.expert == 'adapnet':
+        # no single dominant kernel: the whole serialised expert step against the algorithmic conv FLOPs
+        achieved = args.batch * args.steps * flops_img / dt_serial / 1e12
+        roofline = {'bound': 'mfma', 'kernel': 'whole AdapNet step, every kernel (algorithmic conv FLOPs / step time)',
+                    'achieved': round(achieved, 2), 'peak': PEAK_TFLOPS['bf16'], 'unit': 'TFLOP/s',
+                    'frac': round(achieved / PEAK_TFLOPS['bf16'], 4), 'traffic': None,
+                    'gflop_per_image_pair': round(flops_img / 1e9, 2),
+                    'measured': 'wall clock of the serialised eager steps (%.3f ms/step)' % (dt_serial / args.steps * 1e3)}
+    out = {'roofline': roofline}
+    if pair is not None:
+        out['roofline_first_pair'] = pair
+        out['roofline_all_3x3'] = both
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch-norm', action='store_true', help='train mode: the batch_normalization=true training graph')
-    ap.add_argument('--layer-profile', action='store_true', help='print per-conv-launch times of the roofline pass')
+    ap.add_argument('--layer-profile', action='store_true', help='--full: print per-conv-launch times of the roofline pass')
     ap.add_argument('--no-roofline-pass', action='store_true',
-                    help='train mode: skip the per-launch HIP-event pass after the timed region (kernel traces of the step alone)')
+                    help='--full, train mode: skip the per-launch HIP-event pass after the timed region (kernel traces of the '
+                         'step alone)')
     ap.add_argument('--batch', type=int, default=16, help='images per GPU per step')
     ap.add_argument('--height', type=int, default=384)
     ap.add_argument('--width', type=int, default=768)
@@ -782,13 +875,19 @@ def main():
                     help="--dtype fp8: first e4m3 conv, one layer name or rgb=<layer>,depth=<layer> ('bf16': that expert keeps bf16 operands)")
     ap.add_argument('--fp8-deep', action='store_true',
                     help="--dtype fp8: e4m3 operands from conv1_2 on (model config fp8_deep: faster, costs accuracy)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also the per-kernel roofline pass, the CPU baseline, the accuracy evidence and '
+                         'the extra configurations / the train_dp record (each skipped by its --no-* option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB: a '
+                         'fixed sample of a larger output); the same arguments give the same inputs in every run')
     ap.add_argument('--record', default=None, choices=['dirichlet_fit', 'dp_regime'],
-                    help='print ONE of the extra records alone (N = 1) instead of the headline line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-accuracy', action='store_true', help='skip the trained-experts accuracy evidence (N = 1 only)')
+                    help='print ONE of the extra records of --full alone (N = 1) instead of the headline line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-accuracy', action='store_true', help='--full: skip the trained-experts accuracy evidence (N = 1 only)')
     ap.add_argument('--accuracy-steps', type=int, default=1500)
     ap.add_argument('--accuracy-images', type=int, default=24)
-    ap.add_argument('--no-extra', action='store_true', help='skip the extra configurations / the train_dp record')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the extra configurations / the train_dp record')
     ap.add_argument('--dist-backend', default='nccl', help="'nccl' (= RCCL over xGMI); 'gloo' only for smoke tests")
     ap.add_argument('--share-device', action='store_true',
                     help='smoke test: all ranks use GPU 0 (gloo backend only)')
@@ -799,12 +898,16 @@ def main():
     ap.add_argument('--two-streams', action='store_true',
                     help='run the experts side by side on two streams at every batch size (default: the model chooses -- two '
                          'streams for small batches, one from the batch on at which every launch fills the chip)')
-    ap.add_argument('--min-seconds', type=float, default=2.0,
+    ap.add_argument('--min-seconds', type=float, default=0.0,
                     help='the timed block of --steps steps is repeated until this many seconds of timed work; the median '
-                         'block is reported (0 = exactly one block)')
+                         'block is reported (default 0 = exactly one block: --steps timed steps)')
     ap.add_argument('--train-dp-timeout', type=float, default=240.0,
                     help='N > 1: seconds the train_dp phase may take before the headline line is printed without it')
     args = ap.parse_args()
+    if args.layer_profile and not args.full:
+        ap.error('--layer-profile prints the per-launch times of the roofline pass: it needs --full')
+    if args.record is not None:
+        args.full = True            # (an extra record of --full, measured as --full measures it)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return launch_ranks(args)
     # stdout carries exactly ONE JSON line: everything the models print (reference-style INFO / WARNING lines) goes to stderr
@@ -857,47 +960,18 @@ def main():
     batch = synthetic_batch(device, args.batch, args.height, args.width, seed=1234 + rank)
     if args.dtype == 'fp8':
         net.calibrate(batch)
+    last = [] if args.dump_outputs else None
     times, _, prof, times_serial = measure_inference(net, batch, device, args.steps, args.warmup, graph=args.graph,
                                                      serial=True if args.serial_experts else (False if args.two_streams else None),
                                                      world=world, dist=dist,
-                                                     min_seconds=args.min_seconds)
+                                                     min_seconds=args.min_seconds, profile=args.full, last=last)
     dt = float(np.median(times))            # block times are already the max over ranks
-    dt_serial = float(np.median(times_serial))
-
-    if args.layer_profile and rank == 0:
-        # per-launch-slot breakdown (launch order repeats every step): flops, mean time, TFLOP/s
-        per = len(prof) // max(args.steps * len(times_serial), 1)
-        for i in range(per):
-            evs = prof[i::per]
-            ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in evs) / len(evs)
-            print('  conv launch %2d %s %7.1f GF %8.1f us %7.0f TF/s' % (i, evs[0][0], evs[0][1] / 1e9, ms * 1e3,
-                                                                      evs[0][1] / ms / 1e9), file=sys.stderr)
-    # dominant kernel: the 3x3 implicit-GEMM MFMA conv (fp8: the launches on e4m3 operands, against the fp8 peak)
-    pair = both = None
-    if args.dtype == 'fp8':
-        roofline = roofline_of(prof, ('k3f8',), PEAK_TFLOPS['fp8'],
-                               'conv_f8_dma_kernel (v_mfma_scale_f32_32x32x64_f8f6f4, 3x3 launches on e4m3 operands; conv_mfma_kernel<F8> where a map does not tile in 16x32)',
-                               times_serial, args.steps)
-    else:
-        roofline = roofline_of(prof, ('k3',), PEAK_TFLOPS['bf16'],
-                               'conv_dma4_kernel / conv_dma5_kernel (the 3x3 implicit-GEMM MFMA conv: every launch of conv2_1 .. '
-                               'conv5_3; conv_dma_kernel / conv_mfma_kernel on shapes that do not tile)', times_serial,
-                               args.steps, traffic=committed_traffic(args.batch, args.height, args.width))
-        # conv1_1 + conv1_2 run as ONE kernel (conv_first_fused.hip): reported beside the dominant kernel, with the algorithmic
-        # FLOPs of both layers against the whole kernel's time, and both together so that nothing is left out
-        pair = roofline_of(prof, ('k3pair',), PEAK_TFLOPS['bf16'], 'conv_first_pair_kernel (conv1_1 + conv1_2 + pool1 fused; '
-                           'algorithmic FLOPs of both layers)', times_serial, args.steps)
-        both = roofline_of(prof, ('k3', 'k3pair'), PEAK_TFLOPS['bf16'], 'all of the above', times_serial, args.steps)
+    if last and rank == 0:
+        # the fused label map of the last timed step (rank 0's shard): class indices, exact in float32
+        dump_outputs(args.dump_outputs, {'labels': last[0].numpy().astype(np.float32)})
     per_image = conv_flops_per_image if args.expert == 'fcn' else adapnet_flops_per_image
     flops_img = per_image(args.height, args.width, 3) + per_image(args.height, args.width, 1)
-    if args.expert == 'adapnet':
-        # no single dominant kernel: the whole serialised expert step against the algorithmic conv FLOPs
-        achieved = args.batch * args.steps * flops_img / dt_serial / 1e12
-        roofline = {'bound': 'mfma', 'kernel': 'whole AdapNet step, every kernel (algorithmic conv FLOPs / step time)',
-                    'achieved': round(achieved, 2), 'peak': PEAK_TFLOPS['bf16'], 'unit': 'TFLOP/s',
-                    'frac': round(achieved / PEAK_TFLOPS['bf16'], 4), 'traffic': None,
-                    'gflop_per_image_pair': round(flops_img / 1e9, 2),
-                    'measured': 'wall clock of the serialised eager steps (%.3f ms/step)' % (dt_serial / args.steps * 1e3)}
+    roofs = roofline_records(args, prof, times_serial, flops_img, rank) if args.full else {}
 
     # ---- the headline record: complete BEFORE anything below can fail or hang --------------------------------------------
     images = args.batch * world * args.steps
@@ -913,14 +987,11 @@ def main():
                    'expert_streams': 1 if args.serial_experts else (2 if args.two_streams else 'auto: 2 for batches whose launches leave CUs idle, else 1'), 'hip_graph': bool(getattr(net, '_bench_graph_used', args.graph)),
                    'parallelism': 'dp%d (batch sharding, no data-path collective)' % world},
         'conv_tflops_end_to_end': round(images * flops_img / dt / 1e12, 2),
-        'roofline': roofline,
     }
-    if pair is not None:
-        res['roofline_first_pair'] = pair
-        res['roofline_all_3x3'] = both
+    res.update(roofs)
     res.update(block_stats(times, args.steps))
     res['timing'] = ('blocks of exactly --steps steps, barrier + synchronize on both sides, max over ranks, repeated until '
-                     '%.1f s; value and ms_per_step are the MEDIAN block' % args.min_seconds)
+                     '%.1f s (0: one block); value and ms_per_step are the MEDIAN block' % args.min_seconds)
     if args.dtype == 'fp8':
         res['config']['conv_dtype'] = ('e4m3 operands from conv1_2 on (fp8_deep), conv1_1 fp32 -> e4m3' if args.fp8_deep else
                                        'e4m3 operands from conv2_2 on, conv1_1 fp32, conv1_2 bf16, conv2_1 bf16 -> e4m3')
@@ -944,7 +1015,7 @@ def main():
 
     # ---- records beyond the headline ---------------------------------------------------------------------------------
     extra = []
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         variables = dict(net.variables)
         del net
         torch.cuda.empty_cache()
@@ -1035,7 +1106,7 @@ def main():
             guarded(dirichlet_fit_record, device)
         if extra:
             res['extra'] = extra
-    elif world > 1 and not args.no_extra and default_line:
+    elif args.full and world > 1 and not args.no_extra and default_line:
         del net
         torch.cuda.empty_cache()
         # The data-parallel TRAINING step: the collective path an inference scaling curve never touches.  The headline

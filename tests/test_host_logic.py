@@ -613,3 +613,27 @@ def test_bench_launcher_parent_never_touches_the_gpu(monkeypatch, tmp_path):
     with pytest.raises(SystemExit) as e:
         bench.launch_ranks(args)
     assert e.value.code == 2 and not started
+
+
+def test_bench_dump_outputs_fixed_sample_under_the_size_cap(monkeypatch, tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 (float64 kept), whole arrays while they fit, over the cap every array cut to
+    the same fixed sample, so that two runs with the same arguments write the same files."""
+    import importlib
+    monkeypatch.syspath_prepend(ROOT)
+    bench = importlib.import_module('bench')
+    labels = np.arange(4 * 8 * 16).reshape(4, 8, 16) % 12
+    bench.dump_outputs(str(tmp_path / 'small'), {'labels': labels, 'loss': np.array([2.5])})
+    got = np.load(tmp_path / 'small' / 'labels.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, labels)
+    assert np.load(tmp_path / 'small' / 'loss.npy').dtype == np.float64
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 40000)
+    big = {'params': np.random.default_rng(0).standard_normal(30000).astype(np.float32), 'labels': labels}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['labels.npy', 'params.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 40000
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.size > 0 and np.array_equal(a, b)
+    assert np.isin(np.load(tmp_path / 'a' / 'params.npy'), big['params']).all()

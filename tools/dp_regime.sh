@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-TRAIN="python3 $ROOT/bench.py --mode train --no-cpu-baseline --no-accuracy --no-extra"
+TRAIN="python3 $ROOT/bench.py --mode train --full --no-cpu-baseline --no-accuracy --no-extra"
 for b in 4 16; do for v in plain bn; do
   x=""; [ $v = bn ] && x="--batch-norm"
   $TRAIN --batch $b $x --steps 10 --warmup 3 --min-seconds 1.5 "$@" > $OUT/${TAG}_train_b${b}_${v}.json 2> $OUT/${TAG}_train_b${b}_${v}.err

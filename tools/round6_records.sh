@@ -11,9 +11,9 @@ bash $ROOT/tools/bench_records.sh $TAG > $OUT/${TAG}_records.log 2>&1
 cd $ROOT
 python3 bench.py --record dirichlet_fit > $OUT/${TAG}_bench_dirichlet_fit_2048.json 2>/dev/null
 python3 bench.py --record dp_regime > $OUT/${TAG}_bench_dp_regime.json 2>/dev/null
-python3 bench.py --expert adapnet --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy --no-extra > $OUT/${TAG}_bench_adapnet.json 2>/dev/null
-python3 bench.py --mode train --expert adapnet --batch 8 --steps 5 --warmup 2 --no-cpu-baseline --no-accuracy --no-extra > $OUT/${TAG}_bench_adapnet_train.json 2>/dev/null
-python3 bench.py --fusion joint --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy --no-extra > $OUT/${TAG}_bench_fusion_fcn.json 2>/dev/null
+python3 bench.py --full --min-seconds 2 --expert adapnet --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy --no-extra > $OUT/${TAG}_bench_adapnet.json 2>/dev/null
+python3 bench.py --full --min-seconds 2 --mode train --expert adapnet --batch 8 --steps 5 --warmup 2 --no-cpu-baseline --no-accuracy --no-extra > $OUT/${TAG}_bench_adapnet_train.json 2>/dev/null
+python3 bench.py --full --min-seconds 2 --fusion joint --steps 10 --warmup 3 --no-cpu-baseline --no-accuracy --no-extra > $OUT/${TAG}_bench_fusion_fcn.json 2>/dev/null
 python3 tools/wgrad_bench.py --variant 2 > $OUT/${TAG}_wgrad_layers_v2.txt 2>/dev/null
 python3 tools/wgrad_bench.py --variant 3 > $OUT/${TAG}_wgrad_layers_v3.txt 2>/dev/null
 bash $ROOT/tools/dp_regime.sh $TAG > $OUT/${TAG}_dp_regime.log 2>&1

@@ -1,6 +1,6 @@
 import os, sys, time, json
 import numpy as np, torch
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from modular_semantic_segmentation_amd import host_pipeline as hp
 from modular_semantic_segmentation_amd.base_model import iterate_batches
