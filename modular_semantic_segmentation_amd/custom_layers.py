@@ -65,7 +65,8 @@ def dense_deconv_as_conv3x3(kernel, stride):
 # (`variables=`, reference npz schema: numpy arrays or device tensors) and the scope (`scope=`, the model prefix).  Keyword
 # arguments TensorFlow needs and this path does not (`reuse`, `trainable`, initialisers, regularisers, `data_format=
 # 'channels_last'`) are accepted and ignored.  Packed weights are cached per (variables dict, layer): call
-# `clear_layer_cache()` after changing a dict in place.
+# `clear_layer_cache()` after changing a dict in place yourself.  The library's own in-place changes need none: a
+# training-mode batch norm that writes new moving statistics back (`_bn_write_back`) drops the layer's BN-folded packing.
 # =====================================================================================================================
 _LAYER_CACHE = {}         # key (kind, id(variables), ...) -> (variables, payload): the entry keeps the dict alive, so that the
 #                           id in its key cannot be handed to another dict while the entry exists
@@ -172,6 +173,11 @@ def _bn_write_back(variables, scope, name, st, real):
     pre = '%s/%s/' % (scope, name) if scope else name + '/'
     variables[pre + 'moving_mean'] = st['mm'][:real].cpu().numpy().copy()
     variables[pre + 'moving_variance'] = st['mv'][:real].cpu().numpy().copy()
+    # conv2d(training=False) caches its kernel and bias with the OLD moving statistics folded in: drop that entry, so the
+    # next inference call folds the new ones (the unfolded packing of training mode stays)
+    stale = ('conv', id(variables), pre + 'kernel', True)
+    for key in [key for key in _LAYER_CACHE if key[:4] == stale]:
+        del _LAYER_CACHE[key]
 
 
 def conv2d(inputs, filters, kernel_size, batch_normalization=False, training=False, variables=None, scope='', **kwargs):

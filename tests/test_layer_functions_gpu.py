@@ -101,6 +101,49 @@ def test_conv2d_training_mode_batch_norm_updates_the_moving_statistics(cl):
     assert np.abs(v['m/c/moving_variance'] - before['m/c/moving_variance']).max() > 1e-4      # updated (UPDATE_OPS)
 
 
+@pytest.mark.parametrize('layer', ['conv3x3', 'score'])
+def test_conv2d_inference_after_a_training_call_folds_the_new_moving_statistics(cl, layer):
+    """conv2d(batch_normalization=True, training=False) caches its kernel and bias with the moving statistics folded in;
+    a training-mode call on the same dict writes new moving statistics back, and the next inference call must use them:
+    bit for bit what a fresh copy of the updated dict gives, and within float32 / bf16 rounding of the float64 fold."""
+    rng = np.random.default_rng(5)
+    cout = 64 if layer == 'conv3x3' else 12
+    k = 3 if layer == 'conv3x3' else 1
+    x = torch.from_numpy(_bf(rng.normal(0, 1, (2, 16, 24, 64)))).cuda()
+    v = {'m/c/kernel': _bf(rng.normal(0, 0.05, (k, k, 64, cout))), 'm/c/bias': rng.normal(0, 0.1, cout).astype(np.float32)}
+    v.update(_bn_vars(rng, 'm/c', cout))
+    # a moving variance far below the batch's: one update moves the folded scale by a factor of 1.5 .. 4
+    v['m/c/moving_variance'] = rng.uniform(0, 1e-3, cout).astype(np.float32)
+    kw = dict(batch_normalization=True, name='c', activation='relu' if layer == 'conv3x3' else None, padding='same',
+              variables=v, scope='m')
+
+    def out(y):
+        return y.real().cpu().numpy() if layer == 'conv3x3' else y.cpu().numpy()
+    old = {k_: a.copy() for k_, a in v.items()}
+    cl.conv2d(x, cout, k, training=False, **kw)                              # caches the fold of the old statistics
+    cl.conv2d(x, cout, k, training=True, **kw)                               # writes new moving statistics into v
+    got = out(cl.conv2d(x, cout, k, training=False, **kw))
+    fresh = {k_: a.copy() for k_, a in v.items()}
+    kw['variables'] = fresh
+    want = out(cl.conv2d(x, cout, k, training=False, **kw))
+    torch.cuda.synchronize()
+    assert (v['m/c/moving_variance'] > 1.5 * old['m/c/moving_variance'] + 5e-4).all()
+    assert np.array_equal(got, want)
+    xr = x.cpu().numpy().astype(np.float64)
+    z = _nhwc(fo.conv2d_same(_nchw(xr), v['m/c/kernel'].astype(np.float64), v['m/c/bias'].astype(np.float64)))
+
+    def fold(vv):
+        s = vv['m/c/gamma'].astype(np.float64) / np.sqrt(vv['m/c/moving_variance'].astype(np.float64) + 1e-3)
+        r = z * s + (vv['m/c/beta'] - vv['m/c/moving_mean'].astype(np.float64) * s)
+        return np.maximum(r, 0) if layer == 'conv3x3' else r
+    ref, stale = fold(v), fold(old)
+    got = got[..., :cout]
+    # conv3x3: bf16 operands of the folded weights and a bf16 output (2 ulp of the largest value); score: fp32 (1e-4)
+    rel = 2 * BF16_EPS if layer == 'conv3x3' else 1e-4
+    _close(got, ref, rel=rel, what=layer + ' after a training call')
+    assert np.abs(got - stale).max() > 10 * rel * np.abs(ref).max()          # the old fold is far outside that bound
+
+
 @pytest.mark.parametrize('stride,bn', [(2, False), (8, False), (8, True), (2, True)])
 def test_deconv2d_bilinear_matches_conv2d_transpose(cl, stride, bn):
     rng = np.random.default_rng(10 + stride)
