@@ -249,6 +249,14 @@ int xv_upsample2x_affine_act_add(const xv_act* x, const float* scale, const floa
  * stream: masks are reproducible per seed, not comparable with the reference's.                                    */
 int xv_dropout(const xv_act* x, const xv_act* y, float rate, uint64_t seed, void* stream);
 
+/* MC-dropout samples of one map (the variance fusion model, variance_mix.py:33-83): y holds num_samples + 1 slots of x's
+ * n images, slot-major (y->n == (num_samples + 1) x->n); slot 0 = x, slot t = xv_dropout(x, rate, seed0 + (t-1) stride) bit
+ * for bit (the hash takes the index within the slot; the whole padded slot is written).  The in-place form drops slots
+ * 1 .. num_samples of y with the same seeds and leaves slot 0 as it is. */
+int xv_dropout_samples(const xv_act* x, const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride,
+                       void* stream);
+int xv_dropout_samples_inplace(const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride, void* stream);
+
 /* y = concat(a, b) along channels (tf.concat(axis=3) of the two trunks' conv4_3 / conv5_3, fusion_fcn.py:27-28). */
 int xv_concat_channels(const xv_act* a, const xv_act* b, const xv_act* y, void* stream);
 
@@ -366,6 +374,11 @@ int xv_dirichlet_fuse(const float* const* probs, int num_experts, const float* a
 /* Mean of the experts' probabilities then argmax (average_mix.py:18-21).                         */
 int xv_average_fuse(const float* const* probs, int num_experts, int num_classes, int64_t npix,
                     int64_t* fused, void* stream);
+/* variance_mix.py:7-15: fused = sum_e probs_e / (1e-20 + var_e) / sum_e 1 / (1e-20 + var_e) per pixel (variances: one float
+ * per pixel and expert) -> its argmax (fused, optional) and the fused score itself (fused_score [npix][C], optional); the
+ * fusion step of xv_variance_head_fwd, bit for bit. */
+int xv_variance_fuse(const float* const* probs, const float* const* variances, int num_experts, int num_classes,
+                     int64_t npix, int64_t* fused, float* fused_score, void* stream);
 
 /* ---- training: backward kernels and optimizers ---------------------------------------------------
  * These replace the gradient graph tf.train.{Adam,RMSProp,Adagrad}Optimizer.minimize(self.loss)
@@ -453,6 +466,15 @@ int xv_score_lowres(const xv_act* fused, const float* w_score, int num_classes, 
 int xv_fused_head_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi, int wi,
                       int num_classes, int mode, const float* tab, const float* lognorm, const float* logprior,
                       int64_t* fused_label, void* stream);
+
+/* Variance head of the MC-dropout fusion model (variance_mix.py:7-15,33-83): Sa / Sb = xv_score_lowres of each expert's
+ * (T+1) n-image map (slot 0 plain, slots 1..T dropout samples; T = num_samples) -> per output pixel and expert the softmax of
+ * every pass, the variance over the T samples averaged over the classes, and the certainty-weighted fusion of the plain
+ * passes' probabilities -> label int64 [n][8hi][8wi].  Optional (null skips): fused_score float [n][8hi][8wi][C], probs
+ * float [2][n][8hi][8wi][C] (the plain passes' softmax, bits of xv_decoder_head_fwd's prob), variance float [2][n][8hi][8wi]. */
+int xv_variance_head_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi, int wi,
+                         int num_classes, int num_samples, int64_t* label, float* fused_score, float* probs, float* variance,
+                         void* stream);
 
 /* Loss and head backward (simple_fcn.py:212-214, utils.py:43-53) in the same commuted form: recomputes
  * score = bilinear_x8(fused . Ws) + bs, adds -sum(onehot*log_softmax)/(1e-20+count) to *loss, accumulates

@@ -11,6 +11,7 @@ def get_model(name):
     from .average_mix import AverageFusion
     from .fusion_fcn import FusionFCN
     from .adapnet import Adapnet
+    from .variance_mix import VarianceFusion
     if name == 'fcn':
         return SimpleFCN
     elif name == 'fusion_fcn':
@@ -23,4 +24,6 @@ def get_model(name):
         return DirichletFusion
     elif name in ['average_fusion', 'average_mix']:
         return AverageFusion
+    elif name in ['variance_mix', 'variance_fusion']:
+        return VarianceFusion
     raise UserWarning('ERROR: Model %s not found' % name)

@@ -123,11 +123,12 @@ def paired_from(model, inputs):
     return gi
 
 
-def run_trunks(model, inputs, finish):
+def run_trunks(model, inputs, finish, pair=True):
     """Both experts up to finish(modality, state-or-None) -> result: each on its own HIP stream (the experts are independent
     until the fusion kernel); from paired_from() on the layers both experts share are ONE launch each on the current stream
     -- whole rounds of workgroups where each expert alone leaves its last round half empty -- and the streams fork again for
-    the heads.  The current stream waits for all of them before returning."""
+    the heads.  The current stream waits for all of them before returning.  pair=False: no paired section (finish runs the
+    whole trunk of each expert on its own)."""
     from .fcn import encoder_layers_pair
     mods = model.modalities
     conc = expert_streams(model, inputs)
@@ -150,7 +151,7 @@ def run_trunks(model, inputs, finish):
                 main.wait_stream(model._expert_streams[m])
         return out
 
-    gi = paired_from(model, inputs)
+    gi = paired_from(model, inputs) if pair else None
     if gi is None:
         return each(lambda m: finish(m, None))
     st = each(lambda m: model.experts[m].encoder_begin(inputs[m], stop=gi))

@@ -352,6 +352,29 @@ __global__ __launch_bounds__(256) void average_fuse_kernel(ProbPtrs probs, int E
   }
 }
 
+// variance_mix.py:7-15 (variance_fusion): the certainty-weighted mean of the experts' probabilities, certainty = 1 / (1e-20 +
+// variance) per expert and pixel, and its argmax -- the fusion step of the variance head (pointwise.hip) through the same device
+// functions (xv_common.h), so that the head's own probabilities and variances fed in here give its labels bit for bit.
+template <int CMAX>
+__global__ __launch_bounds__(256) void variance_fuse_kernel(ProbPtrs probs, ProbPtrs vars, int E, int C, int64_t npix,
+                                                           int64_t* __restrict__ fused, float* __restrict__ score, int vec) {
+  for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * 256) {
+    float acc[CMAX], csum;
+    for (int e = 0; e < E; ++e) {
+      float x[CMAX];
+      load_row<CMAX>(probs.p[e] + pix * C, C, vec, x);
+      xv_variance_fuse_add<CMAX>(acc, csum, x, vars.p[e][pix], e == 0);
+    }
+    const int bi = xv_variance_fuse_finish<CMAX>(acc, csum, C);
+    if (fused) fused[pix] = bi;
+    if (score) {
+#pragma unroll
+      for (int k = 0; k < CMAX; ++k)
+        if (k < C) score[pix * C + k] = acc[k];
+    }
+  }
+}
+
 // dirichlet_mix.py:142-163: S[label][k] += log(1e-10 + p[k]); counts[label] += 1.
 // A workgroup keeps `rep` double copies of the [C][C] table (and of the counts) in LDS (16 for C <= 20, fewer beyond: the
 // host fits them into 64 KB), copy = lane & (rep - 1) in the fastest-varying position: the lanes of a wave spread over the
@@ -578,6 +601,28 @@ extern "C" int xv_average_fuse(const float* const* probs, int num_experts, int n
   else
     hipLaunchKernelGGL(average_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, pp, num_experts, num_classes, npix,
                        fused, vec);
+  return xv_launch_status();
+}
+
+extern "C" int xv_variance_fuse(const float* const* probs, const float* const* variances, int num_experts, int num_classes,
+                                int64_t npix, int64_t* fused, float* fused_score, void* stream) {
+  XV_CHECK_ARG(probs && variances && (fused || fused_score));
+  XV_CHECK_SHAPE(num_experts >= 1 && num_experts <= MAXE && num_classes >= 1 && num_classes <= 32 && npix > 0);
+  ProbPtrs pp{}, vp{};
+  for (int e = 0; e < num_experts; ++e) {
+    XV_CHECK_ARG(probs[e] && variances[e]);
+    pp.p[e] = probs[e];
+    vp.p[e] = variances[e];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int vec = (num_classes & 3) == 0;
+  for (int e = 0; e < num_experts; ++e) vec = vec && ((uintptr_t)probs[e] & 15) == 0;
+  if (num_classes <= 16)
+    hipLaunchKernelGGL(variance_fuse_kernel<16>, dim3(grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
+                       npix, fused, fused_score, vec);
+  else
+    hipLaunchKernelGGL(variance_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
+                       npix, fused, fused_score, vec);
   return xv_launch_status();
 }
 

@@ -875,6 +875,97 @@ __global__ __launch_bounds__(256) void fused_head_kernel(const float* __restrict
   }
 }
 
+// ---- variance head of the MC-dropout fusion model (variance_mix.py:7-15,33-83): both experts' low-resolution class scores of
+// T + 1 passes each (slot-major: images 0 .. N-1 are the plain pass, t N .. t N + N-1 dropout sample t; xv_score_lowres of the
+// (T+1) N-image maps) -> per output pixel and expert: the probabilities p_t of every sample (head_logits / head_max /
+// head_softmax: the bits of decoder_head_kernel's `prob`), their population variance over the T samples per class
+// (tf.nn.moments over the sample axis) averaged over the classes, and the probabilities of the plain pass -> the
+// certainty-weighted fusion (xv_variance_fuse_add / _finish, shared with xv_variance_fuse) -> the fused label.  The moments
+// take two passes over the samples, each RECOMPUTING p_t from the taps (nothing of size T C is held): the mean of the
+// deviations d_t = p_t - p_1 from the first sample, then the mean of (d_t - mean)^2 -- the variance of p itself; shifting by a
+// sample keeps identical samples at a variance of exactly 0 (the mean of T equal fp32 values, summed and scaled, need not be
+// that value).  Optional outputs: fused score [N][8Hi][8Wi][C], plain probabilities [2][N][8Hi][8Wi][C], variance
+// [2][N][8Hi][8Wi].  One output pixel per thread.
+template <int CM>
+__device__ __forceinline__ void head_prob(const float* __restrict__ S, const float* __restrict__ bs_g, int n, int oy, int ox,
+                                          int Hi, int Wi, int C, float (&sc)[CM]) {
+  head_logits<CM>(S, bs_g, n, oy, ox, Hi, Wi, C, sc);
+  const float m = head_max<CM>(sc, C);
+  head_softmax<CM>(sc, m, C);
+}
+
+template <int CM>
+__global__ __launch_bounds__(256) void variance_head_kernel(const float* __restrict__ Sa, const float* __restrict__ Sb,
+                                                           const float* __restrict__ ba, const float* __restrict__ bb, int N,
+                                                           int Hi, int Wi, int C, int T, int64_t* __restrict__ label,
+                                                           float* __restrict__ score, float* __restrict__ prob,
+                                                           float* __restrict__ var_out) {
+  const int Ho = Hi * 8, Wo = Wi * 8;
+  const int64_t npix = (int64_t)N * Ho * Wo;
+  const int64_t opix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (opix >= npix) return;
+  const int ox = (int)(opix % Wo);
+  const int oy = (int)((opix / Wo) % Ho);
+  const int n = (int)(opix / ((int64_t)Wo * Ho));
+  const float invT = 1.f / (float)T;
+  const float invTC = 1.f / (float)(T * C);
+  float var[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float* S = e == 0 ? Sa : Sb;
+    const float* bs = e == 0 ? ba : bb;
+    float p1[CM], mean[CM], sc[CM];
+    head_prob<CM>(S, bs, N + n, oy, ox, Hi, Wi, C, p1);
+#pragma unroll
+    for (int k = 0; k < CM; ++k) mean[k] = 0.f;
+    for (int t = 2; t <= T; ++t) {
+      head_prob<CM>(S, bs, t * N + n, oy, ox, Hi, Wi, C, sc);
+#pragma unroll
+      for (int k = 0; k < CM; ++k) mean[k] += sc[k] - p1[k];
+    }
+    float sq[CM];
+#pragma unroll
+    for (int k = 0; k < CM; ++k) {
+      mean[k] = mean[k] * invT;
+      sq[k] = mean[k] * mean[k];  // sample 1: d_1 = 0
+    }
+    for (int t = 2; t <= T; ++t) {
+      head_prob<CM>(S, bs, t * N + n, oy, ox, Hi, Wi, C, sc);
+#pragma unroll
+      for (int k = 0; k < CM; ++k) {
+        const float d = (sc[k] - p1[k]) - mean[k];
+        sq[k] = __builtin_fmaf(d, d, sq[k]);
+      }
+    }
+    float vs = 0.f;
+#pragma unroll
+    for (int k = 0; k < CM; ++k)
+      if (k < C) vs += sq[k];
+    var[e] = vs * invTC;
+  }
+  float acc[CM], csum;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    float sc[CM];
+    head_prob<CM>(e == 0 ? Sa : Sb, e == 0 ? ba : bb, n, oy, ox, Hi, Wi, C, sc);
+    if (prob) {
+      float* dst = prob + ((int64_t)e * npix + opix) * C;
+#pragma unroll
+      for (int k = 0; k < CM; ++k)
+        if (k < C) dst[k] = sc[k];
+    }
+    if (var_out) var_out[(int64_t)e * npix + opix] = var[e];
+    xv_variance_fuse_add<CM>(acc, csum, sc, var[e], e == 0);
+  }
+  const int l = xv_variance_fuse_finish<CM>(acc, csum, C);
+  label[opix] = l;
+  if (score) {
+#pragma unroll
+    for (int k = 0; k < CM; ++k)
+      if (k < C) score[opix * C + k] = acc[k];
+  }
+}
+
 // The Dirichlet form of fused_head_kernel for C == CM on PACKED fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32, two classes per
 // instruction): every per-class step of the scalar form that is not a summation chain -- the four-tap interpolation, the bias,
 // x - max, the products with log2 e / 1 / sum / ln 2, fma(p, 1 / sum', 1e-20), dot - lognorm, + logprior -- is the same IEEE
@@ -1416,20 +1507,39 @@ __device__ __forceinline__ uint32_t xv_mix32(uint64_t z) {  // splitmix64 finali
   return (uint32_t)((z ^ (z >> 31)) >> 32);
 }
 
+// the eight channels idx * 8 .. idx * 8 + 7 of a map dropped with `seed` (idx: index of the 16-byte group within the map)
+__device__ __forceinline__ u32x4 dropout8(u32x4 v, int64_t idx, uint32_t drop_below, float scale, uint64_t seed) {
+  u32x4 o;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t r0 = xv_mix32(seed ^ (uint64_t)(idx * 8 + 2 * w) * 0xd1342543de82ef95ull);
+    const uint32_t r1 = xv_mix32(seed ^ (uint64_t)(idx * 8 + 2 * w + 1) * 0xd1342543de82ef95ull);
+    const float lo = r0 >= drop_below ? bf16_bits_to_f32(v[w] & 0xffffu) * scale : 0.f;
+    const float hi = r1 >= drop_below ? __builtin_bit_cast(float, v[w] & 0xffff0000u) * scale : 0.f;
+    o[w] = pack_bf16x2(lo, hi);
+  }
+  return o;
+}
+
 __global__ __launch_bounds__(256) void dropout_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t total8,
                                                      uint32_t drop_below, float scale, uint64_t seed) {
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total8; idx += (int64_t)gridDim.x * 256) {
-    const u32x4 v = x[idx];
-    u32x4 o;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const uint32_t r0 = xv_mix32(seed ^ (uint64_t)(idx * 8 + 2 * w) * 0xd1342543de82ef95ull);
-      const uint32_t r1 = xv_mix32(seed ^ (uint64_t)(idx * 8 + 2 * w + 1) * 0xd1342543de82ef95ull);
-      const float lo = r0 >= drop_below ? bf16_bits_to_f32(v[w] & 0xffffu) * scale : 0.f;
-      const float hi = r1 >= drop_below ? __builtin_bit_cast(float, v[w] & 0xffff0000u) * scale : 0.f;
-      o[w] = pack_bf16x2(lo, hi);
-    }
-    y[idx] = o;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total8; idx += (int64_t)gridDim.x * 256)
+    y[idx] = dropout8(x[idx], idx, drop_below, scale, seed);
+}
+
+// MC-dropout samples of one map (the variance fusion model): y holds T + 1 slots of the N-image map x, slot-major; slot 0 is
+// x itself, slot t = 1 .. T is x dropped with seed0 + (t - 1) * stride -- bit for bit what dropout_kernel writes for that seed:
+// the hash takes the element's index WITHIN its slot.  blockIdx.y = slot - first_slot; the whole padded slot is written (its
+// border is x's zero border).  In place (x == y, first_slot = 1): slot 0 is left as it is and slot t is read from itself.
+__global__ __launch_bounds__(256) void dropout_samples_kernel(const u32x4* x, u32x4* y, int64_t slot8, int first_slot,
+                                                             uint32_t drop_below, float scale, uint64_t seed0, uint64_t stride) {
+  const int slot = (int)blockIdx.y + first_slot;
+  const u32x4* src = x == y ? y + slot * slot8 : x;
+  u32x4* dst = y + slot * slot8;
+  const uint64_t seed = seed0 + (uint64_t)(slot - 1) * stride;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < slot8; idx += (int64_t)gridDim.x * 256) {
+    const u32x4 v = src[idx];
+    dst[idx] = slot == 0 ? v : dropout8(v, idx, drop_below, scale, seed);
   }
 }
 
@@ -1442,6 +1552,39 @@ extern "C" int xv_dropout(const xv_act* x, const xv_act* y, float rate, uint64_t
   const double thr = (double)rate * 4294967296.0;
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, (const u32x4*)x->data,
                      (u32x4*)y->data, total8, (uint32_t)(thr > 4294967295.0 ? 4294967295.0 : thr), 1.f / (1.f - rate), seed);
+  return xv_launch_status();
+}
+
+static uint32_t dropout_threshold(float rate) {
+  const double thr = (double)rate * 4294967296.0;
+  return (uint32_t)(thr > 4294967295.0 ? 4294967295.0 : thr);
+}
+
+extern "C" int xv_dropout_samples(const xv_act* x, const xv_act* y, int num_samples, float rate, uint64_t seed0,
+                                  uint64_t stride, void* stream) {
+  XV_REQUIRE_BF16(x, y);
+  XV_CHECK_ARG(x && y && x->data && y->data && rate >= 0.f && rate < 1.f && num_samples >= 1 && num_samples <= 1024);
+  XV_CHECK_SHAPE(x->n > 0 && (int64_t)y->n == (int64_t)x->n * (num_samples + 1) && x->h == y->h && x->w == y->w &&
+                 x->c == y->c && (x->c & 7) == 0 && xv_dims_sane(y->n, y->h, y->w));
+  const int64_t slot8 = (int64_t)x->n * (x->h + 2) * (x->w + 2) * (x->c >> 3);
+  const char* xb = (const char*)x->data;
+  const char* yb = (const char*)y->data;
+  XV_CHECK_ARG(xb + slot8 * 16 <= yb || yb + (num_samples + 1) * slot8 * 16 <= xb);  // out of place: disjoint buffers
+  hipLaunchKernelGGL(dropout_samples_kernel, dim3(grid_for(slot8, 256, 2048), num_samples + 1), dim3(256), 0,
+                     (hipStream_t)stream, (const u32x4*)x->data, (u32x4*)y->data, slot8, 0, dropout_threshold(rate),
+                     1.f / (1.f - rate), seed0, stride);
+  return xv_launch_status();
+}
+
+extern "C" int xv_dropout_samples_inplace(const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride,
+                                          void* stream) {
+  XV_REQUIRE_BF16(y);
+  XV_CHECK_ARG(y && y->data && rate >= 0.f && rate < 1.f && num_samples >= 1 && num_samples <= 1024);
+  XV_CHECK_SHAPE(y->n > 0 && y->n % (num_samples + 1) == 0 && (y->c & 7) == 0 && xv_dims_sane(y->n, y->h, y->w));
+  const int64_t slot8 = (int64_t)(y->n / (num_samples + 1)) * (y->h + 2) * (y->w + 2) * (y->c >> 3);
+  hipLaunchKernelGGL(dropout_samples_kernel, dim3(grid_for(slot8, 256, 2048), num_samples), dim3(256), 0,
+                     (hipStream_t)stream, (const u32x4*)y->data, (u32x4*)y->data, slot8, 1, dropout_threshold(rate),
+                     1.f / (1.f - rate), seed0, stride);
   return xv_launch_status();
 }
 
@@ -1532,6 +1675,35 @@ extern "C" int xv_fused_head_fwd(const float* Sa, const float* Sb, const float* 
     default: XV_FH(32); break;
   }
 #undef XV_FH
+  return xv_launch_status();
+}
+
+// Variance head of the MC-dropout fusion model (see variance_head_kernel): Sa / Sb from xv_score_lowres of each expert's
+// (T+1) n-image `fused` map, [(T+1) n][hi+2][wi+2][CP] each.
+extern "C" int xv_variance_head_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                                    int wi, int num_classes, int num_samples, int64_t* label, float* fused_score, float* probs,
+                                    float* variance, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && label);
+  XV_CHECK_SHAPE(num_classes >= 1 && num_classes <= 32 && num_samples >= 1 && num_samples <= 1024);
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi) && (int64_t)n * (num_samples + 1) < ((int64_t)1 << 31));
+  const int64_t npix = (int64_t)n * hi * wi * 64;
+  XV_CHECK_SHAPE((npix + 255) / 256 <= 0x7fffffff);
+  const unsigned grid = (unsigned)((npix + 255) / 256);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_VH(CMV)                                                                                                    \
+  hipLaunchKernelGGL(variance_head_kernel<CMV>, dim3(grid), dim3(256), 0, s, Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, \
+                     num_samples, label, fused_score, probs, variance)
+  switch ((num_classes + 3) / 4) {
+    case 1: XV_VH(4); break;
+    case 2: XV_VH(8); break;
+    case 3: XV_VH(12); break;
+    case 4: XV_VH(16); break;
+    case 5: XV_VH(20); break;
+    case 6: XV_VH(24); break;
+    case 7: XV_VH(28); break;
+    default: XV_VH(32); break;
+  }
+#undef XV_VH
   return xv_launch_status();
 }
 

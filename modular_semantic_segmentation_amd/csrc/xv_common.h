@@ -162,6 +162,37 @@ __device__ static __forceinline__ float xv_fast_exp(float x) { return __builtin_
 __device__ static __forceinline__ float xv_fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 __device__ static __forceinline__ float xv_fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
+// Certainty-weighted fusion of the MC-dropout model (variance_mix.py:7-15): fused[k] = sum_e p_e[k] c_e / sum_e c_e with the
+// certainty c_e = 1 / (1e-20 + var_e).  The variance head (pointwise.hip) and xv_variance_fuse (fusion.hip) both run these two
+// functions, experts in the same order, so their labels agree bit for bit.  Contraction is off inside them: a caller's
+// product must not be fused into `1e-20 + var` in one kernel and not in the other.
+template <int CM>
+__device__ static __forceinline__ void xv_variance_fuse_add(float (&acc)[CM], float& csum, const float (&p)[CM], float var,
+                                                             bool first) {
+#pragma clang fp contract(off)
+  const float c = 1.f / (1e-20f + var);
+#pragma unroll
+  for (int k = 0; k < CM; ++k) acc[k] = first ? p[k] * c : __builtin_fmaf(p[k], c, acc[k]);
+  csum = first ? c : csum + c;
+}
+
+// acc <- the fused score; returns its argmax over the first C classes (lowest index on ties, tf.argmax)
+template <int CM>
+__device__ static __forceinline__ int xv_variance_fuse_finish(float (&acc)[CM], float csum, int C) {
+#pragma clang fp contract(off)
+  float best = 0.f;
+  int bi = 0;
+#pragma unroll
+  for (int k = 0; k < CM; ++k) {
+    acc[k] = acc[k] / csum;
+    if (k < C && (k == 0 || acc[k] > best)) {
+      best = acc[k];
+      bi = k;
+    }
+  }
+  return bi;
+}
+
 // Order-preserving map of packed bf16 bit patterns onto signed 16-bit integers (an involution: negative values have their
 // magnitude bits flipped), for a 2x2 max on packed pairs WITHOUT a preceding relu.
 __device__ static __forceinline__ uint32_t pk_ord_bf16(uint32_t x) {

@@ -190,6 +190,8 @@ class FcnEngine(object):
         # tf.layers.dropout(training=True) is applied -- 'pool3', 'conv4_3', 'conv5_3' in the encoder, 'features' for the
         # decoder input -- at rate dropout_rate; every forward pass draws new masks (dropout_seed + pass counter)
         self.dropout_layers, self.dropout_rate, self.dropout_seed, self._dropout_pass = (), 0.0, 0, 0
+        # mc_lowres_scores: most images one launch of the replicated part of the trunk sees (the samples run in chunks)
+        self.mc_chunk_images = 64
         self._arena = {}
         self.load(variables)
 
@@ -537,10 +539,70 @@ class FcnEngine(object):
             raise NotImplementedError("dropout sites exist in the bf16 graph only (conv_dtype='fp8' is plain inference)")
         self.dropout_layers, self.dropout_rate, self.dropout_seed = tuple(dropout_layers), float(dropout_rate), int(seed)
 
-    def _dropout(self, x, tag):
+    @staticmethod
+    def _dropout_seed_of(dropout_seed, dropout_pass, tag):
         site = sum(ord(ch) for ch in tag)
-        seed = (self.dropout_seed * 0x9E3779B1 + self._dropout_pass * 1000003 + site) & 0xffffffffffffffff
+        return (dropout_seed * 0x9E3779B1 + dropout_pass * 1000003 + site) & 0xffffffffffffffff
+
+    def _dropout(self, x, tag):
+        seed = self._dropout_seed_of(self.dropout_seed, self._dropout_pass, tag)
         return ops.dropout(x, self.dropout_rate, seed, y=self._act(tag, x.n, x.h, x.w, x.c))
+
+    def mc_lowres_scores(self, x, num_samples, rate, seed, st=None):
+        """The passes of the MC-dropout (variance fusion) model: the plain pass and `num_samples` passes with the dropout sites
+        'pool3' (after pool3 and pool4) at `rate`, as low-resolution class scores float32 [(T+1) N][h/8+2][w/8+2][CP],
+        slot-major (slot 0 the plain pass, slot t sample t; lowres_scores of each).  Everything up to pool3 is the same for
+        all of them and runs ONCE; pool3 is then replicated into T + 1 slots (slot t dropped, ops.dropout_samples), and conv4_1
+        on runs as one batch of (T+1) N images, pool4 dropped in place.  Sample t uses dropout pass p0 + t-1 with
+        the seeds of _dropout (p0: the engine's pass counter, which advances by T): the bits of T sequential
+        set_dropout(['pool3'], rate, seed) + lowres_scores passes.  Samples run in chunks of at most mc_chunk_images images
+        per launch (each chunk with its own copy of the plain slot; masks are per sample, so chunking changes no bit).
+        st: an encoder state (encoder_begin without dropout) to continue instead of `x`."""
+        if self.conv_dtype != 'bf16':
+            raise NotImplementedError("dropout sites exist in the bf16 graph only (conv_dtype='fp8' is plain inference)")
+        if not self.commuted_head():
+            raise NotImplementedError('mc_lowres_scores needs the commuted decoder head (bilinear x8 deconv, no batch norm '
+                                      'shift before its relu)')
+        if self._drop_fn() is not None:
+            raise ValueError('mc_lowres_scores draws its own masks: disable the dropout sites (set_dropout([], 0)) first')
+        T = int(num_samples)
+        if T < 1:
+            raise ValueError('num_samples must be at least 1')
+        names = [e[0] for e in ENCODER]
+        i41, i43 = names.index('conv4_1'), names.index('conv4_3')
+        if st is None:
+            st = self.encoder_begin(x, stop=i41)
+        elif st['keep_all'] or st['next'] > i41:
+            raise ValueError('mc_lowres_scores(st=...): an encoder state begun without keep_all, before conv4_1')
+        self.encoder_layers(st, i41)
+        n, h, w = st['n'], st['h'], st['w']
+        pool3 = st['cur']
+        cp = (self.C + 3) // 4 * 4
+        key = ('mc_S', T, n, h // 8, w // 8)
+        S = self._arena.get(key)
+        if S is None:
+            S = self._arena[key] = torch.zeros(((T + 1) * n, h // 8 + 2, w // 8 + 2, cp), dtype=torch.float32,
+                                               device=self.device)
+        per = max(1, int(self.mc_chunk_images) // n - 1)        # samples per chunk (+ the plain slot)
+        p0 = self._dropout_pass
+        a = 0
+        while a < T:
+            k = min(per, T - a)
+            m = (k + 1) * n
+            rep = self._act('pool3_mc', m, pool3.h, pool3.w, pool3.c)
+            ops.dropout_samples(pool3, k, rate, self._dropout_seed_of(seed, p0 + a, 'pool3_drop'), 1000003, y=rep)
+            sc = {'n': m, 'h': h, 'w': w, 'keep_all': False, 'routed': False, 'L': {}, 'cur': rep, 'ch': pool3.h,
+                  'cw': pool3.w, 'next': i41}
+            self.encoder_layers(sc, i43 + 1)
+            ops.dropout_samples(sc['cur'], k, rate, self._dropout_seed_of(seed, p0 + a, 'pool4_drop'), 1000003, in_place=True)
+            f = self.encoder_finish(sc)['fused']
+            if a == 0:
+                ops.score_lowres(f, self.w['score'], self.C, S[:m])
+            else:      # the samples alone; the chunk's plain slot repeats slot 0
+                ops.score_lowres(f.images(n, m), self.w['score'], self.C, S[(1 + a) * n:(1 + a + k) * n])
+            a += k
+        self._dropout_pass = p0 + T
+        return S, (n, h // 8, w // 8)
 
     def commuted_head(self):
         """True if the decoder head runs in its commuted form (class scores interpolated at 1/8 resolution): no batch-norm

@@ -57,6 +57,14 @@ class Act(object):
         v = self.interior().float()
         return v * (2.0 ** self.scale_exp) if self.dtype == 'fp8' else v
 
+    def images(self, n0, n1):
+        """Images n0 .. n1-1 as an Act sharing this one's storage (a slot of a slot-major batch)."""
+        v = Act.__new__(Act)
+        v.n, v.h, v.w, v.c, v.dtype, v.scale_exp = int(n1) - int(n0), self.h, self.w, self.c, self.dtype, self.scale_exp
+        v.t = self.t[int(n0):int(n1)]
+        v._xv = xv_act(v.t.data_ptr(), v.n, v.h, v.w, v.c, self._xv.dtype, self.scale_exp)
+        return v
+
     @classmethod
     def from_dense(cls, x, dtype='bf16', scale_exp=0):
         """Test helper: pad a dense NHWC float tensor into a new Act (rounds to the storage dtype; fp8 stores
@@ -493,6 +501,22 @@ def dropout(x, rate, seed, y=None):
     return y
 
 
+def dropout_samples(x, num_samples, rate, seed0, stride, y=None, in_place=False):
+    """MC-dropout samples of x (xv_dropout_samples): an Act of (num_samples + 1) * x.n images, slot-major -- slot 0 = x, slot t
+    = dropout(x, rate, seed0 + (t - 1) * stride).  in_place=True: x already holds the slots; drop slots 1.. of it (slot 0
+    untouched) and return x."""
+    T = int(num_samples)
+    seed0, stride = int(seed0) & 0xffffffffffffffff, int(stride) & 0xffffffffffffffff
+    if in_place:
+        _lib.check(_lib.lib().xv_dropout_samples_inplace(x.xv(), T, float(rate), seed0, stride, _stream()),
+                   'xv_dropout_samples_inplace')
+        return x
+    if y is None:
+        y = Act((T + 1) * x.n, x.h, x.w, x.c, x.t.device)
+    _lib.check(_lib.lib().xv_dropout_samples(x.xv(), y.xv(), T, float(rate), seed0, stride, _stream()), 'xv_dropout_samples')
+    return y
+
+
 def concat_channels(a, b, y=None):
     if y is None:
         y = Act(a.n, a.h, a.w, a.c + b.c, a.t.device)
@@ -565,6 +589,33 @@ def fused_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, tab, logprior, lo
     return out
 
 
+def variance_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, num_samples, want_score=False, want_probs=False,
+                  want_variance=False):
+    """Both experts' low-resolution scores of (num_samples + 1) * n images each (slot 0 plain, then the dropout samples) ->
+    dict 'label' (int64 [n, 8hi, 8wi]) and, where asked, 'fused_score' (float32 [n, 8hi, 8wi, C]), 'probs' (float32 [2, n,
+    8hi, 8wi, C]: the plain passes' softmax) and 'variance' (float32 [2, n, 8hi, 8wi])."""
+    for t, name in ((Sa, 'Sa'), (Sb, 'Sb'), (bias_a, 'bias_a'), (bias_b, 'bias_b')):
+        _need(t, torch.float32, name)
+    T, C = int(num_samples), int(num_classes)
+    cp = (C + 3) // 4 * 4
+    for t in (Sa, Sb):
+        if tuple(t.shape) != ((T + 1) * n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores of shape %s, expected %s' % (tuple(t.shape), ((T + 1) * n, hi + 2, wi + 2, cp)))
+    dev, ho, wo = Sa.device, 8 * hi, 8 * wi
+    out = {'label': torch.empty((n, ho, wo), dtype=torch.int64, device=dev)}
+    if want_score:
+        out['fused_score'] = torch.empty((n, ho, wo, C), dtype=torch.float32, device=dev)
+    if want_probs:
+        out['probs'] = torch.empty((2, n, ho, wo, C), dtype=torch.float32, device=dev)
+    if want_variance:
+        out['variance'] = torch.empty((2, n, ho, wo), dtype=torch.float32, device=dev)
+    rc = _lib.lib().xv_variance_head_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C, T, _ptr(out['label']),
+                                        _ptr(out.get('fused_score')), _ptr(out.get('probs')), _ptr(out.get('variance')),
+                                        _stream())
+    _lib.check(rc, 'xv_variance_head_fwd')
+    return out
+
+
 def softmax_argmax(score, want_prob=True, want_label=True):
     _need(score, torch.float32, 'score')
     c = score.shape[-1]
@@ -626,6 +677,28 @@ def average_fuse(probs):
     rc = _lib.lib().xv_average_fuse(_ptr_array(probs), len(probs), c, probs[0].numel() // c, _ptr(fused), _stream())
     _lib.check(rc, 'xv_average_fuse')
     return fused
+
+
+def variance_fuse(probs, variances, want_score=True, want_label=True):
+    """variance_mix.py:7-15 on E experts: probs float32 [..., C] each, variances float32 [...] (one per pixel) -> (fused label
+    int64 [...] or None, fused score float32 [..., C] or None)."""
+    for p in probs:
+        _need(p, torch.float32, 'probs')
+    for v in variances:
+        _need(v, torch.float32, 'variances')
+    if len(probs) != len(variances) or not probs:
+        raise ValueError('one variance map per probability map')
+    c = probs[0].shape[-1]
+    shape = tuple(probs[0].shape[:-1])
+    if any(tuple(p.shape) != shape + (c,) for p in probs) or any(tuple(v.shape) != shape for v in variances):
+        raise ValueError('probability maps [..., C] and variance maps [...] of one shape')
+    dev = probs[0].device
+    fused = torch.empty(shape, dtype=torch.int64, device=dev) if want_label else None
+    score = torch.empty(shape + (c,), dtype=torch.float32, device=dev) if want_score else None
+    rc = _lib.lib().xv_variance_fuse(_ptr_array(probs), _ptr_array(variances), len(probs), c, probs[0].numel() // c,
+                                    _ptr(fused), _ptr(score), _stream())
+    _lib.check(rc, 'xv_variance_fuse')
+    return fused, score
 
 
 def dirichlet_suffstats(prob, labels, S, counts):

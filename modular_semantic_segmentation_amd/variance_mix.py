@@ -1,0 +1,82 @@
+"""MC-dropout variance fusion (reference: xview/models/variance_mix.py; timed by experiments/timing.py:181-218).
+
+Per modality the FCN expert runs `num_samples` passes with dropout after pool3 and pool4 (dropout_layers=['pool3']) and one
+pass without; the variance of the samples' softmax over the samples, averaged over the classes, weighs the plain pass's
+probabilities: fused = sum_m prob_m / (1e-20 + var_m) / sum_m 1 / (1e-20 + var_m), label = argmax(fused).  Here the layers
+before the first dropout site run once per expert, the T + 1 passes from conv4_1 on as one batch (FcnEngine.mc_lowres_scores),
+and one kernel takes both experts' low-resolution scores to the fused labels (ops.variance_head)."""
+import torch
+
+from . import ops
+from .basic_fusion_model import FusionModel, run_trunks
+
+
+def variance_fusion(probs, variances):
+    """Functional entry point with the reference's signature (variance_mix.py:7-15): probs, a list of float32 CUDA tensors
+    [N,H,W,C]; variances, one float32 tensor [N,H,W] (or [N,H,W,1]) per expert -> the fused score float32 [N,H,W,C]."""
+    probs = [p.contiguous() for p in probs]
+    shape = tuple(probs[0].shape[:-1])
+    variances = [v.reshape(shape).contiguous() for v in variances]
+    _, score = ops.variance_fuse(probs, variances, want_score=True, want_label=False)
+    return score
+
+
+class VarianceFusion(FusionModel):
+    """config: num_units, num_classes (via data_description), prefixes {modality: prefix} (or modalities, a list: each its own
+    prefix), num_channels, expert_model ('fcn' only, as in the reference), dropout_rate, num_samples; dropout_seed (default:
+    seed, else 0); mc_chunk_images (default 64: most images one launch of the sampled layers sees).  output_attr 'fused_score',
+    'probs' ([N, E, H, W, C]: the plain passes' softmax) and 'variance' ([N, E, H, W]) return the optional outputs of the head.
+    Every call draws new masks (the engines' pass counters advance by num_samples), so the step is never captured into a
+    hipGraph: a replay would redraw the masks of the captured call."""
+
+    def __init__(self, output_dir=None, **config):
+        standard_config = {'learning_rate': 0.0}
+        standard_config.update(config)
+        if 'prefixes' not in standard_config and 'modalities' in standard_config:
+            standard_config['prefixes'] = {m: m for m in standard_config['modalities']}
+        for key in ('dropout_rate', 'num_samples'):
+            if key not in standard_config:
+                raise UserWarning('ERROR: VarianceFusion needs %s in its config' % key)
+        if standard_config.get('expert_model', 'fcn') != 'fcn':
+            raise UserWarning('ERROR: VarianceFusion samples FCN experts only (expert_model=%r)' % standard_config['expert_model'])
+        standard_config['expert_model'] = 'fcn'
+        FusionModel.__init__(self, 'VarianceFusion', output_dir=output_dir, **standard_config)
+
+    def _build_graph(self):
+        FusionModel._build_graph(self)
+        if len(self.modalities) != 2:
+            raise UserWarning('ERROR: VarianceFusion fuses two experts, got %d' % len(self.modalities))
+        rate, T = float(self.config['dropout_rate']), int(self.config['num_samples'])
+        if not 0.0 <= rate < 1.0 or T < 1:
+            raise ValueError('dropout_rate must lie in [0, 1) and num_samples be at least 1')
+        for e in self.experts.values():
+            if not e.commuted_head():
+                raise NotImplementedError('VarianceFusion needs experts with the commuted decoder head (bilinear x8 deconv)')
+            e.mc_chunk_images = int(self.config.get('mc_chunk_images', 64))
+        seed = self.config.get('dropout_seed', self.config.get('seed'))
+        self._dropout_seed = int(seed) if seed is not None else 0
+
+    def _graph_capturable(self):
+        return False
+
+    def _predict_batch_impl(self, batch, output_attr=None):
+        inputs = {m: self._to_device(batch[m], torch.float32) for m in self.modalities}
+        rate, T = float(self.config['dropout_rate']), int(self.config['num_samples'])
+        seeds = {m: self._dropout_seed + i for i, m in enumerate(self.modalities)}     # independent masks per expert
+        # pair=False: the plain trunks stop at pool3 -- a paired section from conv4_1 on would skip the replication
+        res = run_trunks(self, inputs, lambda m, st: self.experts[m].mc_lowres_scores(inputs[m], T, rate, seeds[m], st=st),
+                         pair=False)
+        a, b = self.modalities
+        n, hi, wi = res[a][1]
+        out = ops.variance_head(res[a][0], res[b][0], self.experts[a].b['score'], self.experts[b].b['score'], n, hi, wi,
+                                self.config['num_classes'], T, want_score=output_attr in ('fused_score', 'score'),
+                                want_probs=output_attr in ('probs', 'prob'), want_variance=output_attr == 'variance')
+        if 'probs' in out:
+            self.probs = {m: out['probs'][i] for i, m in enumerate(self.modalities)}
+            return out['probs'].transpose(0, 1).contiguous()
+        if 'variance' in out:
+            self.variances = {m: out['variance'][i] for i, m in enumerate(self.modalities)}
+            return out['variance'].transpose(0, 1).contiguous()
+        if 'fused_score' in out:
+            return out['fused_score']
+        return out['label']
