@@ -257,6 +257,14 @@ int xv_dropout_samples(const xv_act* x, const xv_act* y, int num_samples, float 
                        void* stream);
 int xv_dropout_samples_inplace(const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride, void* stream);
 
+/* The same without the plain slot (the MC-dropout Bayesian FCN, bayesian_fcn.py:74-89, computes T samples and no plain
+ * pass): y->n == num_samples x->n, slot t = xv_dropout(x, rate, seed0 + t stride) bit for bit, t = 0 .. num_samples-1.  The
+ * in-place form drops every slot of y. */
+int xv_dropout_samples_only(const xv_act* x, const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride,
+                            void* stream);
+int xv_dropout_samples_only_inplace(const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride,
+                                    void* stream);
+
 /* y = concat(a, b) along channels (tf.concat(axis=3) of the two trunks' conv4_3 / conv5_3, fusion_fcn.py:27-28). */
 int xv_concat_channels(const xv_act* a, const xv_act* b, const xv_act* y, void* stream);
 
@@ -380,6 +388,14 @@ int xv_average_fuse(const float* const* probs, int num_experts, int num_classes,
 int xv_variance_fuse(const float* const* probs, const float* const* variances, int num_experts, int num_classes,
                      int64_t npix, int64_t* fused, float* fused_score, void* stream);
 
+/* bayesian_fcn.py:48-57 (sampling_uncertainty) on materialised samples float [num_samples][npix][C]: mean_prob [npix][C] = the
+ * mean over the samples, label = its argmax (lowest index on ties), entropy = H(mean) / ln C, cond_entropy = mean_t H(p_t) /
+ * ln C with H(p) = -sum_c p_c ln(clip(p_c, 1e-10, 1)), variance = sum_c population variance over the samples (>= 0; exactly 0
+ * for identical samples).  Every output is optional (null skips), at least one is needed; the reduction of
+ * xv_mc_uncertainty_head_fwd, bit for bit. */
+int xv_sampling_uncertainty(const float* samples, int num_samples, int num_classes, int64_t npix, int64_t* label,
+                            float* mean_prob, float* entropy, float* cond_entropy, float* variance, void* stream);
+
 /* ---- training: backward kernels and optimizers ---------------------------------------------------
  * These replace the gradient graph tf.train.{Adam,RMSProp,Adagrad}Optimizer.minimize(self.loss)
  * builds (base_model.py:153-162) over SimpleFCN's training graph (simple_fcn.py:200-214).
@@ -475,6 +491,16 @@ int xv_fused_head_fwd(const float* Sa, const float* Sb, const float* bias_a, con
 int xv_variance_head_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi, int wi,
                          int num_classes, int num_samples, int64_t* label, float* fused_score, float* probs, float* variance,
                          void* stream);
+
+/* Uncertainty head of the MC-dropout Bayesian FCN (bayesian_fcn.py:48-57, custom_layers.py:251-256): S = xv_score_lowres of
+ * the T n-image map of one expert, sample-major (images t n .. t n + n-1 are sample t = 0 .. T-1, T = num_samples; no plain
+ * slot) -> per output pixel the softmax of every sample (bits of xv_decoder_head_fwd's prob) and from them label int64
+ * [n][8hi][8wi] = argmax of the mean and, optional (null skips): mean_prob float [n][8hi][8wi][C], entropy, cond_entropy,
+ * variance float [n][8hi][8wi] as xv_sampling_uncertainty defines them.  XV_EINVAL for num_samples < 1, num_classes < 2 or a
+ * null label. */
+int xv_mc_uncertainty_head_fwd(const float* S, const float* bias, int n, int hi, int wi, int num_classes, int num_samples,
+                               int64_t* label, float* mean_prob, float* entropy, float* cond_entropy, float* variance,
+                               void* stream);
 
 /* Loss and head backward (simple_fcn.py:212-214, utils.py:43-53) in the same commuted form: recomputes
  * score = bilinear_x8(fused . Ws) + bs, adds -sum(onehot*log_softmax)/(1e-20+count) to *loss, accumulates

@@ -12,6 +12,7 @@ def get_model(name):
     from .fusion_fcn import FusionFCN
     from .adapnet import Adapnet
     from .variance_mix import VarianceFusion
+    from .bayesian_fcn import BayesianFCN
     if name == 'fcn':
         return SimpleFCN
     elif name == 'fusion_fcn':
@@ -26,4 +27,6 @@ def get_model(name):
         return AverageFusion
     elif name in ['variance_mix', 'variance_fusion']:
         return VarianceFusion
+    elif name == 'bayesian_fcn':
+        return BayesianFCN
     raise UserWarning('ERROR: Model %s not found' % name)

@@ -64,6 +64,8 @@ SIGNATURES = {
     'xv_dropout': (_i, [_actp, _actp, ctypes.c_float, ctypes.c_uint64, _vp]),
     'xv_dropout_samples': (_i, [_actp, _actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'xv_dropout_samples_inplace': (_i, [_actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    'xv_dropout_samples_only': (_i, [_actp, _actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    'xv_dropout_samples_only_inplace': (_i, [_actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'xv_conv2d_fwd_residual': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _vp]),
     'xv_subsample2': (_i, [_actp, _actp, _vp]),
     'xv_gather_conv7s2': (_i, [_actp, _actp, _vp]),
@@ -87,6 +89,7 @@ SIGNATURES = {
     'xv_dirichlet_fuse': (_i, [_vpp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     'xv_average_fuse': (_i, [_vpp, _i, _i, _i64, _vp, _vp]),
     'xv_variance_fuse': (_i, [_vpp, _vpp, _i, _i, _i64, _vp, _vp, _vp]),
+    'xv_sampling_uncertainty': (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xv_pack_conv_weights_dgrad': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'xv_pack_conv_weights_multi': (_i, [_vp, _i, _vp]),
     'xv_memset_zero': (_i, [_vp, ctypes.c_size_t, _vp]),
@@ -109,6 +112,7 @@ SIGNATURES = {
     'xv_score_lowres': (_i, [_actp, _vp, _i, _vp, _vp]),
     'xv_fused_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'xv_variance_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'xv_mc_uncertainty_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xv_decoder_head_bwd_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
     'xv_decoder_head_bwd': (_i, [_actp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _actp, _vp, ctypes.c_size_t, _vp]),
     'xv_bn_stats': (_i, [_actp, _vp, _vp]),

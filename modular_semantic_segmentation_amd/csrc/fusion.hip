@@ -375,6 +375,39 @@ __global__ __launch_bounds__(256) void variance_fuse_kernel(ProbPtrs probs, Prob
   }
 }
 
+// bayesian_fcn.py:48-57 (sampling_uncertainty) on MATERIALISED samples [T][npix][C]: mean over the samples and its argmax,
+// normed entropy of the mean, mean normed entropy of the samples, class-summed population variance -- the reduction of the
+// uncertainty head (pointwise.hip, mc_uncertainty_head_kernel) through the same device functions (xv_common.h), samples in the
+// same order, so that the head's own p_t fed in here give its outputs bit for bit.
+template <int CMAX>
+__global__ __launch_bounds__(256) void sampling_uncertainty_kernel(const float* __restrict__ samples, int T, int C, int64_t npix,
+                                                                  float ln_c, int64_t* __restrict__ label,
+                                                                  float* __restrict__ mean_out, float* __restrict__ ent_out,
+                                                                  float* __restrict__ cond_out, float* __restrict__ var_out,
+                                                                  int vec) {
+  const bool want_ce = cond_out != nullptr, want_var = var_out != nullptr;
+  for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * 256) {
+    float mean[CMAX], m2[CMAX], x[CMAX], ce;
+    load_row<CMAX>(samples + pix * C, C, vec, x);
+    xv_mc_first<CMAX>(mean, m2, ce, x, C, want_ce);
+    for (int t = 1; t < T; ++t) {
+      load_row<CMAX>(samples + ((int64_t)t * npix + pix) * C, C, vec, x);
+      xv_mc_add<CMAX>(mean, m2, ce, x, t + 1, C, want_ce, want_var);
+    }
+    float ent, cond, var;
+    const int bi = xv_mc_finish<CMAX>(mean, m2, ce, T, C, ln_c, ent_out != nullptr, ent, cond, var);
+    if (label) label[pix] = bi;
+    if (mean_out) {
+#pragma unroll
+      for (int k = 0; k < CMAX; ++k)
+        if (k < C) mean_out[pix * C + k] = mean[k];
+    }
+    if (ent_out) ent_out[pix] = ent;
+    if (cond_out) cond_out[pix] = cond;
+    if (var_out) var_out[pix] = var;
+  }
+}
+
 // dirichlet_mix.py:142-163: S[label][k] += log(1e-10 + p[k]); counts[label] += 1.
 // A workgroup keeps `rep` double copies of the [C][C] table (and of the counts) in LDS (16 for C <= 20, fewer beyond: the
 // host fits them into 64 KB), copy = lane & (rep - 1) in the fastest-varying position: the lanes of a wave spread over the
@@ -623,6 +656,23 @@ extern "C" int xv_variance_fuse(const float* const* probs, const float* const* v
   else
     hipLaunchKernelGGL(variance_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
                        npix, fused, fused_score, vec);
+  return xv_launch_status();
+}
+
+extern "C" int xv_sampling_uncertainty(const float* samples, int num_samples, int num_classes, int64_t npix, int64_t* label,
+                                       float* mean_prob, float* entropy, float* cond_entropy, float* variance, void* stream) {
+  XV_CHECK_ARG(samples && (label || mean_prob || entropy || cond_entropy || variance) && num_samples >= 1 && num_classes >= 2);
+  XV_CHECK_SHAPE(num_samples <= 1024 && num_classes <= 32 && npix > 0 &&
+                 npix <= ((int64_t)1 << 62) / ((int64_t)num_samples * num_classes));
+  const int vec = (num_classes & 3) == 0 && ((uintptr_t)samples & 15) == 0;
+  const float ln_c = xv_ln_classes(num_classes);
+  hipStream_t s = (hipStream_t)stream;
+  if (num_classes <= 16)
+    hipLaunchKernelGGL(sampling_uncertainty_kernel<16>, dim3(grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
+                       npix, ln_c, label, mean_prob, entropy, cond_entropy, variance, vec);
+  else
+    hipLaunchKernelGGL(sampling_uncertainty_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
+                       npix, ln_c, label, mean_prob, entropy, cond_entropy, variance, vec);
   return xv_launch_status();
 }
 

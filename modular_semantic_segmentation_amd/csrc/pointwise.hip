@@ -966,6 +966,52 @@ __global__ __launch_bounds__(256) void variance_head_kernel(const float* __restr
   }
 }
 
+// ---- uncertainty head of the MC-dropout Bayesian FCN (bayesian_fcn.py:48-57, custom_layers.py:251-256): ONE expert's
+// low-resolution class scores of T dropout samples (sample-major: images t N .. t N + N-1 are sample t = 0 .. T-1, no plain
+// slot; xv_score_lowres of the T N-image map) -> per output pixel the probabilities p_t of every sample (head_prob: the bits of
+// decoder_head_kernel's `prob`), then
+//   mean = (1/T) sum_t p_t, label = argmax mean (lowest index on ties), entropy = H(mean) / ln C,
+//   cond_entropy = (1/T) sum_t H(p_t) / ln C, variance = sum_c population variance of p_tc over t,
+// through xv_mc_first / xv_mc_add / xv_mc_finish (xv_common.h; shared with xv_sampling_uncertainty, which therefore gives the
+// same bits on materialised p_t).  Numerics, fixed there: samples in ascending t, classes in ascending c; ONE pass, every
+// sample interpolated once, Welford's running mean and sum of squared deviations (identical samples: variance exactly 0, mean
+// exactly p_1; variance clamped at 0); T = 1: variance 0 and entropy == cond_entropy bit for bit.  Nothing of size T C is
+// held: the running mean, the squared deviations and the current sample -- one register row fewer than variance_head_kernel.
+// The four float outputs are optional; a launch without `cond_entropy` takes no logarithm per sample, one without `variance`
+// keeps no second moment.
+template <int CM>
+__global__ __launch_bounds__(256) void mc_uncertainty_head_kernel(const float* __restrict__ S, const float* __restrict__ bs,
+                                                                 int N, int Hi, int Wi, int C, int T, float ln_c,
+                                                                 int64_t* __restrict__ label, float* __restrict__ mean_out,
+                                                                 float* __restrict__ ent_out, float* __restrict__ cond_out,
+                                                                 float* __restrict__ var_out) {
+  const int Ho = Hi * 8, Wo = Wi * 8;
+  const int64_t npix = (int64_t)N * Ho * Wo;
+  const int64_t opix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (opix >= npix) return;
+  const int ox = (int)(opix % Wo);
+  const int oy = (int)((opix / Wo) % Ho);
+  const int n = (int)(opix / ((int64_t)Wo * Ho));
+  const bool want_ce = cond_out != nullptr, want_var = var_out != nullptr;
+  float mean[CM], m2[CM], sc[CM], ce;
+  head_prob<CM>(S, bs, n, oy, ox, Hi, Wi, C, sc);
+  xv_mc_first<CM>(mean, m2, ce, sc, C, want_ce);
+  for (int t = 1; t < T; ++t) {
+    head_prob<CM>(S, bs, t * N + n, oy, ox, Hi, Wi, C, sc);
+    xv_mc_add<CM>(mean, m2, ce, sc, t + 1, C, want_ce, want_var);
+  }
+  float ent, cond, var;
+  label[opix] = xv_mc_finish<CM>(mean, m2, ce, T, C, ln_c, ent_out != nullptr, ent, cond, var);
+  if (mean_out) {
+#pragma unroll
+    for (int k = 0; k < CM; ++k)
+      if (k < C) mean_out[opix * C + k] = mean[k];
+  }
+  if (ent_out) ent_out[opix] = ent;
+  if (cond_out) cond_out[opix] = cond;
+  if (var_out) var_out[opix] = var;
+}
+
 // The Dirichlet form of fused_head_kernel for C == CM on PACKED fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32, two classes per
 // instruction): every per-class step of the scalar form that is not a summation chain -- the four-tap interpolation, the bias,
 // x - max, the products with log2 e / 1 / sum / ln 2, fma(p, 1 / sum', 1e-20), dot - lognorm, + logprior -- is the same IEEE
@@ -1527,19 +1573,21 @@ __global__ __launch_bounds__(256) void dropout_kernel(const u32x4* __restrict__ 
     y[idx] = dropout8(x[idx], idx, drop_below, scale, seed);
 }
 
-// MC-dropout samples of one map (the variance fusion model): y holds T + 1 slots of the N-image map x, slot-major; slot 0 is
-// x itself, slot t = 1 .. T is x dropped with seed0 + (t - 1) * stride -- bit for bit what dropout_kernel writes for that seed:
-// the hash takes the element's index WITHIN its slot.  blockIdx.y = slot - first_slot; the whole padded slot is written (its
-// border is x's zero border).  In place (x == y, first_slot = 1): slot 0 is left as it is and slot t is read from itself.
-__global__ __launch_bounds__(256) void dropout_samples_kernel(const u32x4* x, u32x4* y, int64_t slot8, int first_slot,
+// MC-dropout samples of one map: y holds `plain` + T slots of the N-image map x, slot-major.  plain = 1 (the variance fusion
+// model): slot 0 is x itself, slot t = 1 .. T is x dropped with seed0 + (t - 1) * stride; plain = 0 (the Bayesian FCN: samples
+// only): slot t = 0 .. T-1 is x dropped with seed0 + t * stride -- bit for bit what dropout_kernel writes for that seed: the
+// hash takes the element's index WITHIN its slot.  blockIdx.y = slot - first_slot; the whole padded slot is written (its
+// border is x's zero border).  In place (x == y, first_slot = plain): a plain slot is left as it is and every other slot is
+// read from itself.
+__global__ __launch_bounds__(256) void dropout_samples_kernel(const u32x4* x, u32x4* y, int64_t slot8, int first_slot, int plain,
                                                              uint32_t drop_below, float scale, uint64_t seed0, uint64_t stride) {
   const int slot = (int)blockIdx.y + first_slot;
   const u32x4* src = x == y ? y + slot * slot8 : x;
   u32x4* dst = y + slot * slot8;
-  const uint64_t seed = seed0 + (uint64_t)(slot - 1) * stride;
+  const uint64_t seed = seed0 + (uint64_t)(slot - plain) * stride;
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < slot8; idx += (int64_t)gridDim.x * 256) {
     const u32x4 v = src[idx];
-    dst[idx] = slot == 0 ? v : dropout8(v, idx, drop_below, scale, seed);
+    dst[idx] = slot < plain ? v : dropout8(v, idx, drop_below, scale, seed);
   }
 }
 
@@ -1571,7 +1619,7 @@ extern "C" int xv_dropout_samples(const xv_act* x, const xv_act* y, int num_samp
   const char* yb = (const char*)y->data;
   XV_CHECK_ARG(xb + slot8 * 16 <= yb || yb + (num_samples + 1) * slot8 * 16 <= xb);  // out of place: disjoint buffers
   hipLaunchKernelGGL(dropout_samples_kernel, dim3(grid_for(slot8, 256, 2048), num_samples + 1), dim3(256), 0,
-                     (hipStream_t)stream, (const u32x4*)x->data, (u32x4*)y->data, slot8, 0, dropout_threshold(rate),
+                     (hipStream_t)stream, (const u32x4*)x->data, (u32x4*)y->data, slot8, 0, 1, dropout_threshold(rate),
                      1.f / (1.f - rate), seed0, stride);
   return xv_launch_status();
 }
@@ -1583,8 +1631,38 @@ extern "C" int xv_dropout_samples_inplace(const xv_act* y, int num_samples, floa
   XV_CHECK_SHAPE(y->n > 0 && y->n % (num_samples + 1) == 0 && (y->c & 7) == 0 && xv_dims_sane(y->n, y->h, y->w));
   const int64_t slot8 = (int64_t)(y->n / (num_samples + 1)) * (y->h + 2) * (y->w + 2) * (y->c >> 3);
   hipLaunchKernelGGL(dropout_samples_kernel, dim3(grid_for(slot8, 256, 2048), num_samples), dim3(256), 0,
-                     (hipStream_t)stream, (const u32x4*)y->data, (u32x4*)y->data, slot8, 1, dropout_threshold(rate),
+                     (hipStream_t)stream, (const u32x4*)y->data, (u32x4*)y->data, slot8, 1, 1, dropout_threshold(rate),
                      1.f / (1.f - rate), seed0, stride);
+  return xv_launch_status();
+}
+
+// The sample-only forms (the Bayesian FCN computes T slots, not T + 1): y->n == num_samples x->n, slot t = xv_dropout(x, rate,
+// seed0 + t stride); in place every slot of y is dropped.
+extern "C" int xv_dropout_samples_only(const xv_act* x, const xv_act* y, int num_samples, float rate, uint64_t seed0,
+                                       uint64_t stride, void* stream) {
+  XV_REQUIRE_BF16(x, y);
+  XV_CHECK_ARG(x && y && x->data && y->data && rate >= 0.f && rate < 1.f && num_samples >= 1 && num_samples <= 1024);
+  XV_CHECK_SHAPE(x->n > 0 && (int64_t)y->n == (int64_t)x->n * num_samples && x->h == y->h && x->w == y->w && x->c == y->c &&
+                 (x->c & 7) == 0 && xv_dims_sane(y->n, y->h, y->w));
+  const int64_t slot8 = (int64_t)x->n * (x->h + 2) * (x->w + 2) * (x->c >> 3);
+  const char* xb = (const char*)x->data;
+  const char* yb = (const char*)y->data;
+  XV_CHECK_ARG(xb + slot8 * 16 <= yb || yb + num_samples * slot8 * 16 <= xb);  // out of place: disjoint buffers
+  hipLaunchKernelGGL(dropout_samples_kernel, dim3(grid_for(slot8, 256, 2048), num_samples), dim3(256), 0, (hipStream_t)stream,
+                     (const u32x4*)x->data, (u32x4*)y->data, slot8, 0, 0, dropout_threshold(rate), 1.f / (1.f - rate), seed0,
+                     stride);
+  return xv_launch_status();
+}
+
+extern "C" int xv_dropout_samples_only_inplace(const xv_act* y, int num_samples, float rate, uint64_t seed0, uint64_t stride,
+                                               void* stream) {
+  XV_REQUIRE_BF16(y);
+  XV_CHECK_ARG(y && y->data && rate >= 0.f && rate < 1.f && num_samples >= 1 && num_samples <= 1024);
+  XV_CHECK_SHAPE(y->n > 0 && y->n % num_samples == 0 && (y->c & 7) == 0 && xv_dims_sane(y->n, y->h, y->w));
+  const int64_t slot8 = (int64_t)(y->n / num_samples) * (y->h + 2) * (y->w + 2) * (y->c >> 3);
+  hipLaunchKernelGGL(dropout_samples_kernel, dim3(grid_for(slot8, 256, 2048), num_samples), dim3(256), 0, (hipStream_t)stream,
+                     (const u32x4*)y->data, (u32x4*)y->data, slot8, 0, 0, dropout_threshold(rate), 1.f / (1.f - rate), seed0,
+                     stride);
   return xv_launch_status();
 }
 
@@ -1704,6 +1782,36 @@ extern "C" int xv_variance_head_fwd(const float* Sa, const float* Sb, const floa
     default: XV_VH(32); break;
   }
 #undef XV_VH
+  return xv_launch_status();
+}
+
+// Uncertainty head of the MC-dropout Bayesian FCN (see mc_uncertainty_head_kernel): S from xv_score_lowres of the T n-image
+// `fused` map, [T n][hi+2][wi+2][CP], sample-major.
+extern "C" int xv_mc_uncertainty_head_fwd(const float* S, const float* bias, int n, int hi, int wi, int num_classes,
+                                          int num_samples, int64_t* label, float* mean_prob, float* entropy,
+                                          float* cond_entropy, float* variance, void* stream) {
+  XV_CHECK_ARG(S && bias && label && num_samples >= 1 && num_classes >= 2);
+  XV_CHECK_SHAPE(num_classes <= 32 && num_samples <= 1024);
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi) && (int64_t)n * num_samples < ((int64_t)1 << 31));
+  const int64_t npix = (int64_t)n * hi * wi * 64;
+  XV_CHECK_SHAPE((npix + 255) / 256 <= 0x7fffffff);
+  const unsigned grid = (unsigned)((npix + 255) / 256);
+  const float ln_c = xv_ln_classes(num_classes);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_UH(CMV)                                                                                                          \
+  hipLaunchKernelGGL(mc_uncertainty_head_kernel<CMV>, dim3(grid), dim3(256), 0, s, S, bias, n, hi, wi, num_classes, num_samples, \
+                     ln_c, label, mean_prob, entropy, cond_entropy, variance)
+  switch ((num_classes + 3) / 4) {
+    case 1: XV_UH(4); break;
+    case 2: XV_UH(8); break;
+    case 3: XV_UH(12); break;
+    case 4: XV_UH(16); break;
+    case 5: XV_UH(20); break;
+    case 6: XV_UH(24); break;
+    case 7: XV_UH(28); break;
+    default: XV_UH(32); break;
+  }
+#undef XV_UH
   return xv_launch_status();
 }
 

@@ -1,6 +1,7 @@
 // Shared device/host helpers for libxview_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <initializer_list>
@@ -85,6 +86,10 @@ static inline bool xv_dims_sane(int n, int h, int w) {
   const int64_t rows = (int64_t)n * ((int64_t)h + 2);
   return rows < ((int64_t)1 << 31) && rows * ((int64_t)w + 2) < ((int64_t)1 << 36);
 }
+
+// ln C as the uncertainty kernels divide by it (custom_layers.py:251-256 normalises the entropy to [0, 1]): one host value for
+// the head and the stand-alone reduction
+static inline float xv_ln_classes(int num_classes) { return (float)log((double)num_classes); }
 
 // padded-NHWC geometry helpers
 __host__ __device__ static inline int64_t xv_row_pitch(int w, int c) { return (int64_t)(w + 2) * c; }
@@ -190,6 +195,75 @@ __device__ static __forceinline__ int xv_variance_fuse_finish(float (&acc)[CM], 
       bi = k;
     }
   }
+  return bi;
+}
+
+// Per-pixel moments of the MC-dropout Bayesian FCN (bayesian_fcn.py:48-57 sampling_uncertainty, custom_layers.py:251-256
+// entropy) over T samples p_t of a pixel's class probabilities, ONE pass over the samples (each is seen once), Welford's
+// running form:
+//   first:  mean = p_1, m2 = 0, ce = H(p_1)
+//   add:    d = p_t - mean; mean += d * (1 / t); m2 = fma(d, p_t - mean, m2); ce += H(p_t)       (t = 2 .. T, in this order)
+//   finish: variance = (sum_c max(m2_c, 0)) / T; entropy = H(mean) / ln C; cond_entropy = ce / T / ln C; returns argmax_c mean
+//           (lowest index on ties)
+// with H(p) = -sum_c p_c ln(clip(p_c, 1e-10, 1)), classes in ascending order, xv_fast_log after the clip (no denormal reaches
+// it).  Identical samples give d = 0 at every step: variance exactly 0 and mean exactly p_1 (the mean of T equal fp32 values,
+// summed and scaled, need not be that value); a negative rounding residue of m2 is clamped per class, so variance >= 0.
+// T = 1: mean = p_1, so entropy and cond_entropy are the same expression on the same bits.  Two rows of state (mean, m2) where
+// the shifted sums of variance_head_kernel take three: at 16 classes that is what keeps the head at four waves per SIMD.
+// The head (pointwise.hip, mc_uncertainty_head_kernel) and xv_sampling_uncertainty (fusion.hip) both run these functions, so
+// equal p_t give equal bits; contraction is off inside them so that neither caller's context decides where an fma forms.
+// Lanes k >= C are ignored.
+template <int CM>
+__device__ static __forceinline__ float xv_entropy_sum(const float (&p)[CM], int C) {
+#pragma clang fp contract(off)
+  float h = 0.f;
+#pragma unroll
+  for (int k = 0; k < CM; ++k)
+    if (k < C) h -= p[k] * xv_fast_log(fminf(fmaxf(p[k], 1e-10f), 1.f));
+  return h;
+}
+
+template <int CM>
+__device__ static __forceinline__ void xv_mc_first(float (&mean)[CM], float (&m2)[CM], float& ce, const float (&p)[CM], int C,
+                                                    bool want_ce) {
+#pragma unroll
+  for (int k = 0; k < CM; ++k) mean[k] = p[k], m2[k] = 0.f;
+  ce = want_ce ? xv_entropy_sum<CM>(p, C) : 0.f;
+}
+
+// sample number t (1-based, t >= 2)
+template <int CM>
+__device__ static __forceinline__ void xv_mc_add(float (&mean)[CM], float (&m2)[CM], float& ce, const float (&p)[CM], int t,
+                                                  int C, bool want_ce, bool want_var) {
+#pragma clang fp contract(off)
+  const float inv_t = 1.f / (float)t;
+#pragma unroll
+  for (int k = 0; k < CM; ++k) {
+    const float d = p[k] - mean[k];
+    mean[k] = mean[k] + d * inv_t;
+    if (want_var) m2[k] = __builtin_fmaf(d, p[k] - mean[k], m2[k]);
+  }
+  if (want_ce) ce = ce + xv_entropy_sum<CM>(p, C);
+}
+
+// ln_c = (float)ln C from the host (xv_ln_classes)
+template <int CM>
+__device__ static __forceinline__ int xv_mc_finish(const float (&mean)[CM], const float (&m2)[CM], float ce, int T, int C,
+                                                    float ln_c, bool want_ent, float& entropy, float& cond_entropy,
+                                                    float& variance) {
+#pragma clang fp contract(off)
+  const float inv_t = 1.f / (float)T;
+  float var = 0.f, best = 0.f;
+  int bi = 0;
+#pragma unroll
+  for (int k = 0; k < CM; ++k)
+    if (k < C) {
+      var = var + fmaxf(m2[k], 0.f);
+      if (k == 0 || mean[k] > best) best = mean[k], bi = k;
+    }
+  variance = var * inv_t;
+  entropy = want_ent ? xv_entropy_sum<CM>(mean, C) / ln_c : 0.f;
+  cond_entropy = ce * inv_t / ln_c;
   return bi;
 }
 

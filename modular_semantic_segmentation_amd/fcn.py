@@ -558,16 +558,7 @@ class FcnEngine(object):
         set_dropout(['pool3'], rate, seed) + lowres_scores passes.  Samples run in chunks of at most mc_chunk_images images
         per launch (each chunk with its own copy of the plain slot; masks are per sample, so chunking changes no bit).
         st: an encoder state (encoder_begin without dropout) to continue instead of `x`."""
-        if self.conv_dtype != 'bf16':
-            raise NotImplementedError("dropout sites exist in the bf16 graph only (conv_dtype='fp8' is plain inference)")
-        if not self.commuted_head():
-            raise NotImplementedError('mc_lowres_scores needs the commuted decoder head (bilinear x8 deconv, no batch norm '
-                                      'shift before its relu)')
-        if self._drop_fn() is not None:
-            raise ValueError('mc_lowres_scores draws its own masks: disable the dropout sites (set_dropout([], 0)) first')
-        T = int(num_samples)
-        if T < 1:
-            raise ValueError('num_samples must be at least 1')
+        T = self._mc_check('mc_lowres_scores', num_samples)
         names = [e[0] for e in ENCODER]
         i41, i43 = names.index('conv4_1'), names.index('conv4_3')
         if st is None:
@@ -603,6 +594,126 @@ class FcnEngine(object):
             a += k
         self._dropout_pass = p0 + T
         return S, (n, h // 8, w // 8)
+
+    def _mc_check(self, who, num_samples):
+        """What the batched samplers refuse; returns T"""
+        if self.conv_dtype != 'bf16':
+            raise NotImplementedError("dropout sites exist in the bf16 graph only (conv_dtype='fp8' is plain inference)")
+        if not self.commuted_head():
+            raise NotImplementedError('%s needs the commuted decoder head (bilinear x8 deconv, no batch norm '
+                                      'shift before its relu)' % who)
+        if self._drop_fn() is not None:
+            raise ValueError('%s draws its own masks: disable the dropout sites (set_dropout([], 0)) first' % who)
+        T = int(num_samples)
+        if T < 1:
+            raise ValueError('num_samples must be at least 1')
+        return T
+
+    def mc_sample_scores(self, x, num_samples, rate, seed, dropout_layers, st=None):
+        """The T = `num_samples` passes of the MC-dropout Bayesian FCN (bayesian_fcn.py:74-89): low-resolution class scores
+        float32 [T N][h/8+2][w/8+2][CP], sample-major (images t N .. t N + N-1 are sample t; NO plain slot), each slot the BITS
+        of pass p0 + t of set_dropout(dropout_layers, rate, seed) + lowres_scores(x) (p0: the engine's pass counter, which
+        advances by T; seeds of _dropout, stride 1000003 per pass).  What all samples share runs once on N images, and the
+        samples are replicated at the EARLIEST active site (ops.dropout_samples(sample_only=True): per-SAMPLE seeds inside one
+        batch; later sites are dropped in place):
+          'pool3' listed      conv1_1 .. pool3 once; pool3 replicated and dropped, conv4_1 on as one batch of T N images, pool4
+                              dropped ('pool3' gates both pool dropouts, simple_fcn.py:51-63; 'pool4' alone enables nothing), then
+                              conv4_3 (the full map in front of score_conv4; pool4 comes from the undropped one), conv5_3 and
+                              the decoder's input features where listed;
+          'pool3' not listed  the whole 3x3 trunk through conv5_3 once; conv4_3 -> score_conv4 and conv5_3 -> score_conv5 are
+                              replicated where listed (dropped) or after their score conv (copies), then x2 upsample + add,
+                              'features'; 'features' alone replicates the decoder's input only;
+          no active site      (rate 0, or nothing but 'pool4'): T copies of the plain pass.
+        Samples run in chunks of at most mc_chunk_images images per launch (masks are per sample: chunking changes no bit).
+        st: an encoder state (encoder_begin without dropout and without keep_all) to continue instead of `x`."""
+        T = self._mc_check('mc_sample_scores', num_samples)
+        sites = set(dropout_layers) if float(rate) > 0 else set()
+        pool, d43, d53, dfeat = ('pool3' in sites), ('conv4_3' in sites), ('conv5_3' in sites), ('features' in sites)
+        names = [e[0] for e in ENCODER]
+        i41, i43 = names.index('conv4_1'), names.index('conv4_3')
+        shared = i41 if pool else len(ENCODER)
+        if st is None:
+            st = self.encoder_begin(x, stop=shared)
+        elif st['keep_all'] or st['next'] > shared or 's4' in st:
+            raise ValueError('mc_sample_scores(st=...): an encoder state begun without keep_all, before the first dropout site')
+        self.encoder_layers(st, shared)
+        n, h, w = st['n'], st['h'], st['w']
+        hi, wi = h // 8, w // 8
+        cp = (self.C + 3) // 4 * 4
+        key = ('mcs_S', T, n, hi, wi)
+        S = self._arena.get(key)
+        if S is None:
+            S = self._arena[key] = torch.zeros((T * n, hi + 2, wi + 2, cp), dtype=torch.float32, device=self.device)
+        p0 = self._dropout_pass
+        if not (pool or d43 or d53 or dfeat):
+            S0, _ = self.lowres_scores(st=st)
+            S.view((T, n) + tuple(S.shape[1:])).copy_(S0)
+            self._dropout_pass = p0 + T
+            return S, (n, hi, wi)
+
+        def score_conv(src, name, m):
+            y = self._act(name, m, src.h, src.w, self.Up)
+            ops.conv2d_fwd(src, self.w[name], self.b[name], 1, relu=True, y=y)
+            return y
+
+        def finish(s4, s5, m):           # x2 upsample + skip of ready score maps (encoder_finish's own tail)
+            return self.encoder_finish({'n': m, 'h': h, 'w': w, 'L': {}, 's4': s4, 's5': s5})['fused']
+
+        once = {}
+        if not pool:
+            L = st['L']
+            if not d43:
+                once['s4'] = score_conv(L['conv4_3'], 'score_conv4', n)
+            if not d53:
+                once['s5'] = score_conv(L['conv5_3'], 'score_conv5', n)
+            if not d43 and not d53:
+                once['fused'] = finish(once['s4'], once['s5'], n)
+        per = max(1, int(self.mc_chunk_images) // n)              # samples per chunk
+        a = 0
+        while a < T:
+            k = min(per, T - a)
+            m = k * n
+
+            def drop(act, tag, src=None):
+                """the chunk's k slots of `act` dropped in place, or (src: an n-image map) written from src"""
+                ops.dropout_samples(act if src is None else src, k, rate, self._dropout_seed_of(seed, p0 + a, tag + '_drop'),
+                                    1000003, y=None if src is None else act, in_place=src is None, sample_only=True)
+                return act
+
+            def slots(src, tag, dropped):
+                y = self._act(tag + '_mc', m, src.h, src.w, src.c)
+                if dropped:
+                    return drop(y, tag, src=src)
+                y.t.view((k, n) + tuple(y.t.shape[1:])).copy_(src.t)
+                return y
+
+            if pool:
+                sc = {'n': m, 'h': h, 'w': w, 'keep_all': False, 'routed': False, 'L': {}, 'ch': st['ch'], 'cw': st['cw'],
+                      'cur': slots(st['cur'], 'pool3', True), 'next': i41}
+                self.encoder_layers(sc, i43 + 1)
+                drop(sc['cur'], 'pool4')
+                self.encoder_layers(sc, len(ENCODER))
+                if d43:
+                    drop(sc['L']['conv4_3'], 'conv4_3')
+                if d53:
+                    drop(sc['L']['conv5_3'], 'conv5_3')
+                f = self.encoder_finish(sc)['fused']
+                if dfeat:
+                    drop(f, 'features')
+            elif 'fused' in once:
+                f = slots(once['fused'], 'features', True)
+            else:
+                s4 = (score_conv(slots(L['conv4_3'], 'conv4_3', True), 'score_conv4', m) if d43
+                      else slots(once['s4'], 'score_conv4', False))
+                s5 = (score_conv(slots(L['conv5_3'], 'conv5_3', True), 'score_conv5', m) if d53
+                      else slots(once['s5'], 'score_conv5', False))
+                f = finish(s4, s5, m)
+                if dfeat:
+                    drop(f, 'features')
+            ops.score_lowres(f, self.w['score'], self.C, S[a * n:(a + k) * n])
+            a += k
+        self._dropout_pass = p0 + T
+        return S, (n, hi, wi)
 
     def commuted_head(self):
         """True if the decoder head runs in its commuted form (class scores interpolated at 1/8 resolution): no batch-norm

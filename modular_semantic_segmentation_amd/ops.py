@@ -501,19 +501,20 @@ def dropout(x, rate, seed, y=None):
     return y
 
 
-def dropout_samples(x, num_samples, rate, seed0, stride, y=None, in_place=False):
+def dropout_samples(x, num_samples, rate, seed0, stride, y=None, in_place=False, sample_only=False):
     """MC-dropout samples of x (xv_dropout_samples): an Act of (num_samples + 1) * x.n images, slot-major -- slot 0 = x, slot t
     = dropout(x, rate, seed0 + (t - 1) * stride).  in_place=True: x already holds the slots; drop slots 1.. of it (slot 0
-    untouched) and return x."""
+    untouched) and return x.  sample_only=True (xv_dropout_samples_only): no plain slot -- num_samples * x.n images, slot t =
+    dropout(x, rate, seed0 + t * stride), t = 0 .. num_samples-1; in place every slot of x is dropped."""
     T = int(num_samples)
     seed0, stride = int(seed0) & 0xffffffffffffffff, int(stride) & 0xffffffffffffffff
+    name = 'xv_dropout_samples_only' if sample_only else 'xv_dropout_samples'
     if in_place:
-        _lib.check(_lib.lib().xv_dropout_samples_inplace(x.xv(), T, float(rate), seed0, stride, _stream()),
-                   'xv_dropout_samples_inplace')
+        _lib.check(getattr(_lib.lib(), name + '_inplace')(x.xv(), T, float(rate), seed0, stride, _stream()), name + '_inplace')
         return x
     if y is None:
-        y = Act((T + 1) * x.n, x.h, x.w, x.c, x.t.device)
-    _lib.check(_lib.lib().xv_dropout_samples(x.xv(), y.xv(), T, float(rate), seed0, stride, _stream()), 'xv_dropout_samples')
+        y = Act((T if sample_only else T + 1) * x.n, x.h, x.w, x.c, x.t.device)
+    _lib.check(getattr(_lib.lib(), name)(x.xv(), y.xv(), T, float(rate), seed0, stride, _stream()), name)
     return y
 
 
@@ -613,6 +614,56 @@ def variance_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, num_samples, w
                                         _ptr(out.get('fused_score')), _ptr(out.get('probs')), _ptr(out.get('variance')),
                                         _stream())
     _lib.check(rc, 'xv_variance_head_fwd')
+    return out
+
+
+def mc_uncertainty_head(S, bias, n, hi, wi, num_classes, num_samples, want_mean=False, want_entropy=False,
+                        want_cond_entropy=False, want_variance=False):
+    """One expert's low-resolution scores of num_samples * n images (sample-major dropout samples, no plain slot) -> dict
+    'label' (int64 [n, 8hi, 8wi]: argmax of the samples' mean softmax) and, where asked, 'mean' (float32 [n, 8hi, 8wi, C]),
+    'entropy', 'cond_entropy', 'variance' (float32 [n, 8hi, 8wi]) -- xv_mc_uncertainty_head_fwd."""
+    _need(S, torch.float32, 'S')
+    _need(bias, torch.float32, 'bias')
+    T, C = int(num_samples), int(num_classes)
+    cp = (C + 3) // 4 * 4
+    if tuple(S.shape) != (T * n, hi + 2, wi + 2, cp):
+        raise ValueError('low-resolution scores of shape %s, expected %s' % (tuple(S.shape), (T * n, hi + 2, wi + 2, cp)))
+    dev, ho, wo = S.device, 8 * hi, 8 * wi
+    out = {'label': torch.empty((n, ho, wo), dtype=torch.int64, device=dev)}
+    if want_mean:
+        out['mean'] = torch.empty((n, ho, wo, C), dtype=torch.float32, device=dev)
+    for key, want in (('entropy', want_entropy), ('cond_entropy', want_cond_entropy), ('variance', want_variance)):
+        if want:
+            out[key] = torch.empty((n, ho, wo), dtype=torch.float32, device=dev)
+    rc = _lib.lib().xv_mc_uncertainty_head_fwd(_ptr(S), _ptr(bias), n, hi, wi, C, T, _ptr(out['label']), _ptr(out.get('mean')),
+                                              _ptr(out.get('entropy')), _ptr(out.get('cond_entropy')),
+                                              _ptr(out.get('variance')), _stream())
+    _lib.check(rc, 'xv_mc_uncertainty_head_fwd')
+    return out
+
+
+def sampling_uncertainty(samples, want_label=True, want_mean=True, want_entropy=True, want_cond_entropy=True,
+                         want_variance=True):
+    """bayesian_fcn.py:48-57 on materialised samples float32 [T, ..., C] (xv_sampling_uncertainty) -> dict with the asked of
+    'label' (int64 [...]), 'mean' (float32 [..., C]), 'entropy', 'cond_entropy', 'variance' (float32 [...])."""
+    _need(samples, torch.float32, 'samples')
+    if samples.dim() < 3:
+        raise ValueError('samples of shape [T, ..., C]')
+    T, c = samples.shape[0], samples.shape[-1]
+    shape = tuple(samples.shape[1:-1])
+    dev = samples.device
+    out = {}
+    if want_label:
+        out['label'] = torch.empty(shape, dtype=torch.int64, device=dev)
+    if want_mean:
+        out['mean'] = torch.empty(shape + (c,), dtype=torch.float32, device=dev)
+    for key, want in (('entropy', want_entropy), ('cond_entropy', want_cond_entropy), ('variance', want_variance)):
+        if want:
+            out[key] = torch.empty(shape, dtype=torch.float32, device=dev)
+    rc = _lib.lib().xv_sampling_uncertainty(_ptr(samples), T, c, samples.numel() // (T * c), _ptr(out.get('label')),
+                                           _ptr(out.get('mean')), _ptr(out.get('entropy')), _ptr(out.get('cond_entropy')),
+                                           _ptr(out.get('variance')), _stream())
+    _lib.check(rc, 'xv_sampling_uncertainty')
     return out
 
 
