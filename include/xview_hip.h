@@ -502,6 +502,43 @@ int xv_mc_uncertainty_head_fwd(const float* S, const float* bias, int n, int hi,
                                int64_t* label, float* mean_prob, float* entropy, float* cond_entropy, float* variance,
                                void* stream);
 
+/* ---- uncertainty-weighted Dirichlet fusion (uncertainty_dirichlet_mix.py) ---------------------------------------------
+ * Dropout of the network input, whole pixels at a time (noise_shape [N,H,W,1]): x dense float [n][h][w][cin]; y holds
+ * plain + num_samples slots of it, slot-major: slot 0 a copy of x when plain == 1, sample t = 0 .. num_samples-1 with ONE
+ * Bernoulli(1 - rate) draw per pixel from (seed0 + t stride, index of the pixel within its slot), shared by the pixel's
+ * channels; kept pixels are x * (1 / (1 - rate)) in fp32.  A mask depends on the seed and the pixel alone.  num_samples = 1,
+ * plain = 0 is the single pass.  x and y must not overlap; a slot holds fewer than 2^31 - 2^19 elements. */
+int xv_dropout_pixels_samples(const float* x, int n, int h, int w, int cin, float* y, int num_samples, int plain, float rate,
+                              uint64_t seed0, uint64_t stride, void* stream);
+
+/* Moments pass: Sa / Sb as xv_variance_head_fwd takes them ((T+1) n images each, slot 0 plain, T = num_samples) -> mvar float
+ * [2][n][8hi][8wi], per expert the population variance of each class's probability over the T samples averaged over the
+ * classes (the bits of xv_variance_head_fwd's variance), and vmax float [2], per expert the largest per-class variance over
+ * every pixel, class and image of the call.  vmax is cleared here. */
+int xv_uncertainty_moments(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi, int wi,
+                           int num_classes, int num_samples, float* mvar, float* vmax, void* stream);
+
+/* Fusion head: the plain slots of Sa / Sb -> per expert p = softmax (bits of xv_decoder_head_fwd's prob), mix = mvar / vmax
+ * (0 where vmax is 0), alpha[j][c] = params[e][j][c] (1 - mix) + mix (1 + delta_jc), ll[c] = sum_j (alpha[j][c] - 1)
+ * log(1e-20 + p[j] / sum p) + lgamma(sum_j alpha[j][c]) - sum_j lgamma(alpha[j][c]); score = ll_0 + ll_1 + logprior; label
+ * int64 [n][8hi][8wi] = its argmax (lowest index on ties).  params float [2][C][C], logprior float [C].  Optional (null
+ * skips): fused_score float [n][8hi][8wi][C], probs float [2][n][8hi][8wi][C], mix float [2][n][8hi][8wi]. */
+int xv_uncertainty_dirichlet_head_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                                      int wi, int num_classes, const float* mvar, const float* vmax, const float* params,
+                                      const float* logprior, int64_t* label, float* fused_score, float* probs, float* mix,
+                                      void* stream);
+
+/* The same fusion on materialised tensors of TWO experts: probs two device pointers to float [npix][C], mvar float [2][npix],
+ * vmax float [2] -> fused int64 [npix] and / or fused_score float [npix][C] (either may be null); the per-pixel step of
+ * xv_uncertainty_dirichlet_head_fwd, bit for bit. */
+int xv_uncertainty_dirichlet_fuse(const float* const* probs, const float* mvar, const float* vmax, const float* params,
+                                  const float* logprior, int num_classes, int64_t npix, int64_t* fused, float* fused_score,
+                                  void* stream);
+
+/* One expert's per-class uncertainties float [npix][C] (non-negative) -> mvar float [npix], their mean over the classes, and
+ * vmax float [1], their maximum over every pixel and class.  vmax is cleared here. */
+int xv_uncertainty_weights(const float* uncertainty, int num_classes, int64_t npix, float* mvar, float* vmax, void* stream);
+
 /* Loss and head backward (simple_fcn.py:212-214, utils.py:43-53) in the same commuted form: recomputes
  * score = bilinear_x8(fused . Ws) + bs, adds -sum(onehot*log_softmax)/(1e-20+count) to *loss, accumulates
  * d(score kernel) [U][C] and d(score bias) [C], and writes dfused = d(loss)/d(fused) (bf16 padded NHWC; the

@@ -13,6 +13,7 @@ def get_model(name):
     from .adapnet import Adapnet
     from .variance_mix import VarianceFusion
     from .bayesian_fcn import BayesianFCN
+    from .uncertainty_dirichlet_mix import UncertaintyMix
     if name == 'fcn':
         return SimpleFCN
     elif name == 'fusion_fcn':
@@ -29,4 +30,6 @@ def get_model(name):
         return VarianceFusion
     elif name == 'bayesian_fcn':
         return BayesianFCN
+    elif name in ['uncertainty_mix', 'uncertainty_fusion']:
+        return UncertaintyMix
     raise UserWarning('ERROR: Model %s not found' % name)

@@ -113,6 +113,11 @@ SIGNATURES = {
     'xv_fused_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'xv_variance_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'xv_mc_uncertainty_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xv_dropout_pixels_samples': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    'xv_uncertainty_moments': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'xv_uncertainty_dirichlet_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xv_uncertainty_dirichlet_fuse': (_i, [_vpp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    'xv_uncertainty_weights': (_i, [_vp, _i, _i64, _vp, _vp, _vp]),
     'xv_decoder_head_bwd_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
     'xv_decoder_head_bwd': (_i, [_actp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _actp, _vp, ctypes.c_size_t, _vp]),
     'xv_bn_stats': (_i, [_actp, _vp, _vp]),

@@ -408,6 +408,68 @@ __global__ __launch_bounds__(256) void sampling_uncertainty_kernel(const float* 
   }
 }
 
+// uncertainty_dirichlet_mix.py:18-52 on MATERIALISED tensors of two experts: probabilities [npix][C] each, mvar [2][npix] (the
+// class mean of each expert's uncertainty) and vmax [2] (its maximum) -> the fused score and its argmax -- the per-pixel step
+// of the fusion head (pointwise.hip, uncertainty_dirichlet_head_kernel) through the same device functions (xv_common.h), so
+// that the head's own probabilities, mvar and vmax fed in here give its scores and labels bit for bit.  One pixel per thread,
+// tables in LDS.
+template <int CM>
+__global__ __launch_bounds__(256) void uncertainty_dirichlet_fuse_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
+                                                                        const float* __restrict__ mvar,
+                                                                        const float* __restrict__ vmax,
+                                                                        const float* __restrict__ A_g,
+                                                                        const float* __restrict__ logprior, int C, int64_t npix,
+                                                                        int64_t* __restrict__ fused, float* __restrict__ score,
+                                                                        int vec) {
+  extern __shared__ __attribute__((aligned(16))) float tab[];  // A [2][C][CM], column sums [2][CM], log prior [CM]
+  float* cs = tab + 2 * C * CM;
+  float* lp = cs + 2 * CM;
+  xv_udm_stage<CM>(tab, cs, A_g, C, threadIdx.x, 256);
+  xv_udm_stage<CM>(tab + C * CM, cs + CM, A_g + C * C, C, threadIdx.x, 256);
+  if (threadIdx.x < CM) lp[threadIdx.x] = threadIdx.x < C ? logprior[threadIdx.x] : 0.f;
+  __syncthreads();
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= npix) return;
+  float total[CM];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    float x[CM];
+    load_row<CM>((e == 0 ? pa : pb) + pix * C, C, vec, x);
+    const float mix = xv_udm_mix(mvar[(int64_t)e * npix + pix], vmax[e]);
+    xv_udm_add<CM>(total, x, mix, tab + e * C * CM, cs + e * CM, C, e == 0);
+  }
+  const int bi = xv_udm_finish<CM>(total, lp, C);
+  if (fused) fused[pix] = bi;
+  if (score) {
+#pragma unroll
+    for (int k = 0; k < CM; ++k)
+      if (k < C) score[pix * C + k] = total[k];
+  }
+}
+
+// The mix weight's two ingredients from ONE expert's per-class uncertainties [npix][C] (non-negative):
+// mvar[pix] = (sum_c unc[pix][c]) * (1 / C), classes in ascending order, and *vmax = the maximum over every pixel and class.
+// A bounded grid, the running maximum in a register, one atomic per workgroup (xv_block_max_nonneg).
+template <int CMAX>
+__global__ __launch_bounds__(256) void uncertainty_weights_kernel(const float* __restrict__ unc, int C, int64_t npix, float inv_c,
+                                                                 float* __restrict__ mvar, uint32_t* __restrict__ vmax, int vec) {
+  __shared__ uint32_t red[4];
+  float top = 0.f;
+  for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * 256) {
+    float x[CMAX];
+    load_row<CMAX>(unc + pix * C, C, vec, x);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < CMAX; ++k)
+      if (k < C) {
+        s = s + x[k];
+        top = fmaxf(top, x[k]);
+      }
+    mvar[pix] = s * inv_c;
+  }
+  xv_block_max_nonneg(top, red, vmax);
+}
+
 // dirichlet_mix.py:142-163: S[label][k] += log(1e-10 + p[k]); counts[label] += 1.
 // A workgroup keeps `rep` double copies of the [C][C] table (and of the counts) in LDS (16 for C <= 20, fewer beyond: the
 // host fits them into 64 KB), copy = lane & (rep - 1) in the fastest-varying position: the lanes of a wave spread over the
@@ -673,6 +735,50 @@ extern "C" int xv_sampling_uncertainty(const float* samples, int num_samples, in
   else
     hipLaunchKernelGGL(sampling_uncertainty_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
                        npix, ln_c, label, mean_prob, entropy, cond_entropy, variance, vec);
+  return xv_launch_status();
+}
+
+extern "C" int xv_uncertainty_dirichlet_fuse(const float* const* probs, const float* mvar, const float* vmax, const float* params,
+                                             const float* logprior, int num_classes, int64_t npix, int64_t* fused,
+                                             float* fused_score, void* stream) {
+  XV_CHECK_ARG(probs && probs[0] && probs[1] && mvar && vmax && params && logprior && (fused || fused_score));
+  XV_CHECK_SHAPE(num_classes >= 1 && num_classes <= 32 && npix > 0 && (npix + 255) / 256 <= 0x7fffffff);
+  const int vec = (num_classes & 3) == 0 && (((uintptr_t)probs[0] | (uintptr_t)probs[1]) & 15) == 0;
+  const unsigned grid = (unsigned)((npix + 255) / 256);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_UDF(CMV)                                                                                                        \
+  hipLaunchKernelGGL(uncertainty_dirichlet_fuse_kernel<CMV>, dim3(grid), dim3(256),                                        \
+                     (size_t)(2 * num_classes * CMV + 3 * CMV) * 4, s, probs[0], probs[1], mvar, vmax, params, logprior,    \
+                     num_classes, npix, fused, fused_score, vec)
+  switch ((num_classes + 3) / 4) {
+    case 1: XV_UDF(4); break;
+    case 2: XV_UDF(8); break;
+    case 3: XV_UDF(12); break;
+    case 4: XV_UDF(16); break;
+    case 5: XV_UDF(20); break;
+    case 6: XV_UDF(24); break;
+    case 7: XV_UDF(28); break;
+    default: XV_UDF(32); break;
+  }
+#undef XV_UDF
+  return xv_launch_status();
+}
+
+extern "C" int xv_uncertainty_weights(const float* uncertainty, int num_classes, int64_t npix, float* mvar, float* vmax,
+                                      void* stream) {
+  XV_CHECK_ARG(uncertainty && mvar && vmax && ((uintptr_t)vmax & 3) == 0);
+  XV_CHECK_SHAPE(num_classes >= 1 && num_classes <= 32 && npix > 0);
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(vmax, 0, sizeof(float), s);
+  if (e != hipSuccess) return (int)e;
+  const int vec = (num_classes & 3) == 0 && ((uintptr_t)uncertainty & 15) == 0;
+  const float inv_c = 1.f / (float)num_classes;
+  if (num_classes <= 16)
+    hipLaunchKernelGGL(uncertainty_weights_kernel<16>, dim3(grid_for(npix, 256, 512)), dim3(256), 0, s, uncertainty, num_classes,
+                       npix, inv_c, mvar, reinterpret_cast<uint32_t*>(vmax), vec);
+  else
+    hipLaunchKernelGGL(uncertainty_weights_kernel<32>, dim3(grid_for(npix, 256, 512)), dim3(256), 0, s, uncertainty, num_classes,
+                       npix, inv_c, mvar, reinterpret_cast<uint32_t*>(vmax), vec);
   return xv_launch_status();
 }
 

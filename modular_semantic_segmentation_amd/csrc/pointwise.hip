@@ -1012,6 +1012,126 @@ __global__ __launch_bounds__(256) void mc_uncertainty_head_kernel(const float* _
   if (var_out) var_out[opix] = var;
 }
 
+// ---- uncertainty-weighted Dirichlet fusion (uncertainty_dirichlet_mix.py:18-52,221-233): moments pass and fusion head ------
+// Moments: both experts' low-resolution class scores of T + 1 passes (slot 0 plain, slots 1 .. T input-dropout samples; the
+// contract of variance_head_kernel) -> per expert mvar [2][N][8Hi][8Wi], the population variance of every class's probability
+// over the T samples averaged over the classes, and vmax [2], the largest per-class variance of the expert's whole tensor (the
+// reference's reduce_max over pixels, classes AND images).  The per-pixel moments are variance_head_kernel's two sweeps about
+// sample 1, statement for statement, so mvar carries the bits of that kernel's `variance`.  vmax is a grid-wide maximum that
+// ends on two addresses: a bounded grid (at most 256 workgroups of 512 threads per expert: every CU at four waves per SIMD),
+// pixels in a grid-stride loop, the running maximum in a register, one atomic per workgroup (xv_block_max_nonneg).  The entry
+// point zeroes vmax.
+template <int CM>
+__device__ __forceinline__ float head_sample_moments(const float* __restrict__ S, const float* __restrict__ bs, int N, int n, int oy,
+                                                     int ox, int Hi, int Wi, int C, int T, float invT, float invTC,
+                                                     float& vmax_class) {
+  float p1[CM], mean[CM], sc[CM];
+  head_prob<CM>(S, bs, N + n, oy, ox, Hi, Wi, C, p1);
+#pragma unroll
+  for (int k = 0; k < CM; ++k) mean[k] = 0.f;
+  for (int t = 2; t <= T; ++t) {
+    head_prob<CM>(S, bs, t * N + n, oy, ox, Hi, Wi, C, sc);
+#pragma unroll
+    for (int k = 0; k < CM; ++k) mean[k] += sc[k] - p1[k];
+  }
+  float sq[CM];
+#pragma unroll
+  for (int k = 0; k < CM; ++k) {
+    mean[k] = mean[k] * invT;
+    sq[k] = mean[k] * mean[k];  // sample 1: d_1 = 0
+  }
+  for (int t = 2; t <= T; ++t) {
+    head_prob<CM>(S, bs, t * N + n, oy, ox, Hi, Wi, C, sc);
+#pragma unroll
+    for (int k = 0; k < CM; ++k) {
+      const float d = (sc[k] - p1[k]) - mean[k];
+      sq[k] = __builtin_fmaf(d, d, sq[k]);
+    }
+  }
+  float vs = 0.f, mx = 0.f;
+#pragma unroll
+  for (int k = 0; k < CM; ++k)
+    if (k < C) {
+      vs += sq[k];
+      mx = fmaxf(mx, sq[k]);
+    }
+  vmax_class = mx * invT;
+  return vs * invTC;
+}
+
+template <int CM>
+__global__ __launch_bounds__(512) void uncertainty_moments_kernel(const float* __restrict__ Sa, const float* __restrict__ Sb,
+                                                                 const float* __restrict__ ba, const float* __restrict__ bb,
+                                                                 int N, int Hi, int Wi, int C, int T, float* __restrict__ mvar,
+                                                                 uint32_t* __restrict__ vmax) {
+  __shared__ uint32_t red[8];
+  const int Ho = Hi * 8, Wo = Wi * 8;
+  const int64_t npix = (int64_t)N * Ho * Wo;
+  const int e = blockIdx.y;
+  const float* S = e == 0 ? Sa : Sb;
+  const float* bs = e == 0 ? ba : bb;
+  const float invT = 1.f / (float)T;
+  const float invTC = 1.f / (float)(T * C);
+  float top = 0.f;
+  for (int64_t opix = (int64_t)blockIdx.x * 512 + threadIdx.x; opix < npix; opix += (int64_t)gridDim.x * 512) {
+    const int ox = (int)(opix % Wo);
+    const int oy = (int)((opix / Wo) % Ho);
+    const int n = (int)(opix / ((int64_t)Wo * Ho));
+    float vc;
+    mvar[(int64_t)e * npix + opix] = head_sample_moments<CM>(S, bs, N, n, oy, ox, Hi, Wi, C, T, invT, invTC, vc);
+    top = fmaxf(top, vc);
+  }
+  xv_block_max_nonneg(top, red, vmax + e);
+}
+
+// Fusion head: one output pixel per thread.  Both experts' PLAIN-slot probabilities (head_prob on images 0 .. N-1 of S: the
+// bits of decoder_head_kernel's `prob`), mvar and vmax of the moments pass -> xv_udm_mix / xv_udm_add / xv_udm_finish
+// (xv_common.h; shared with xv_uncertainty_dirichlet_fuse, which gives the same bits on materialised inputs) -> the label.
+// Both experts' parameter tables, their column sums and the log prior sit in LDS.  Optional outputs: fused score
+// [N][8Hi][8Wi][C], plain probabilities [2][N][8Hi][8Wi][C], mix [2][N][8Hi][8Wi].
+template <int CM>
+__global__ __launch_bounds__(256) void uncertainty_dirichlet_head_kernel(
+    const float* __restrict__ Sa, const float* __restrict__ Sb, const float* __restrict__ ba, const float* __restrict__ bb, int N,
+    int Hi, int Wi, int C, const float* __restrict__ mvar, const float* __restrict__ vmax, const float* __restrict__ A_g,
+    const float* __restrict__ logprior, int64_t* __restrict__ label, float* __restrict__ score, float* __restrict__ prob,
+    float* __restrict__ mix_out) {
+  extern __shared__ __attribute__((aligned(16))) float udm_tab[];  // A [2][C][CM], column sums [2][CM], log prior [CM]
+  float* cs = udm_tab + 2 * C * CM;
+  float* lp = cs + 2 * CM;
+  xv_udm_stage<CM>(udm_tab, cs, A_g, C, threadIdx.x, 256);
+  xv_udm_stage<CM>(udm_tab + C * CM, cs + CM, A_g + C * C, C, threadIdx.x, 256);
+  if (threadIdx.x < CM) lp[threadIdx.x] = threadIdx.x < C ? logprior[threadIdx.x] : 0.f;
+  __syncthreads();
+  const int Ho = Hi * 8, Wo = Wi * 8;
+  const int64_t npix = (int64_t)N * Ho * Wo;
+  const int64_t opix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (opix >= npix) return;
+  const int ox = (int)(opix % Wo);
+  const int oy = (int)((opix / Wo) % Ho);
+  const int n = (int)(opix / ((int64_t)Wo * Ho));
+  float total[CM];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    float sc[CM];
+    head_prob<CM>(e == 0 ? Sa : Sb, e == 0 ? ba : bb, n, oy, ox, Hi, Wi, C, sc);
+    if (prob) {
+      float* dst = prob + ((int64_t)e * npix + opix) * C;
+#pragma unroll
+      for (int k = 0; k < CM; ++k)
+        if (k < C) dst[k] = sc[k];
+    }
+    const float mix = xv_udm_mix(mvar[(int64_t)e * npix + opix], vmax[e]);
+    if (mix_out) mix_out[(int64_t)e * npix + opix] = mix;
+    xv_udm_add<CM>(total, sc, mix, udm_tab + e * C * CM, cs + e * CM, C, e == 0);
+  }
+  label[opix] = xv_udm_finish<CM>(total, lp, C);
+  if (score) {
+#pragma unroll
+    for (int k = 0; k < CM; ++k)
+      if (k < C) score[opix * C + k] = total[k];
+  }
+}
+
 // The Dirichlet form of fused_head_kernel for C == CM on PACKED fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32, two classes per
 // instruction): every per-class step of the scalar form that is not a summation chain -- the four-tap interpolation, the bias,
 // x - max, the products with log2 e / 1 / sum / ln 2, fma(p, 1 / sum', 1e-20), dot - lognorm, + logprior -- is the same IEEE
@@ -1666,6 +1786,39 @@ extern "C" int xv_dropout_samples_only_inplace(const xv_act* y, int num_samples,
   return xv_launch_status();
 }
 
+// Dropout of the network INPUT, whole pixels at a time (uncertainty_dirichlet_mix.py:106-116: tf.layers.dropout with
+// noise_shape [N, H, W, 1]): ONE draw per (image, row, column), shared by the pixel's channels; a kept pixel is scaled by
+// 1 / (1 - rate) in fp32.  x is the dense fp32 NHWC input; y holds `plain` + T slots of it, slot-major: slot 0 a copy of x when
+// plain, sample t = 0 .. T-1 dropped with seed0 + t * stride.  The bits are xv_mix32 of (seed, index of the PIXEL within its
+// slot), as dropout8 mixes (seed, element index): a mask depends on nothing else -- not on the launch geometry, the channel
+// count or how the samples are dealt out over calls.  One thread per ELEMENT (coalesced 4-byte accesses; the pixel's hash is
+// recomputed per channel, which a streaming copy of three channels does not notice); blockIdx.y = slot.
+__global__ __launch_bounds__(256) void pixel_dropout_kernel(const float* __restrict__ x, float* __restrict__ y, uint32_t slot_elems,
+                                                           uint32_t cin, int plain, uint32_t drop_below, float scale,
+                                                           uint64_t seed0, uint64_t stride) {
+  const int slot = (int)blockIdx.y;
+  float* dst = y + (int64_t)slot * slot_elems;
+  const uint64_t seed = seed0 + (uint64_t)(slot - plain) * stride;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < slot_elems; i += gridDim.x * 256u) {
+    const float v = x[i];
+    const uint32_t r = xv_mix32(seed ^ (uint64_t)(i / cin) * 0xd1342543de82ef95ull);
+    dst[i] = slot < plain ? v : (r >= drop_below ? v * scale : 0.f);
+  }
+}
+
+extern "C" int xv_dropout_pixels_samples(const float* x, int n, int h, int w, int cin, float* y, int num_samples, int plain,
+                                         float rate, uint64_t seed0, uint64_t stride, void* stream) {
+  XV_CHECK_ARG(x && y && rate >= 0.f && rate < 1.f && num_samples >= 1 && num_samples <= 1024 && (plain == 0 || plain == 1));
+  XV_CHECK_SHAPE(n > 0 && h > 0 && w > 0 && cin > 0 && (int64_t)n * h * w * cin < ((int64_t)1 << 31) - 256 * 2048);
+  const int64_t slot = (int64_t)n * h * w * cin, slots = num_samples + plain;
+  const char* xb = (const char*)x;
+  const char* yb = (const char*)y;
+  XV_CHECK_ARG(xb + slot * 4 <= yb || yb + slots * slot * 4 <= xb);  // out of place: disjoint buffers
+  hipLaunchKernelGGL(pixel_dropout_kernel, dim3(grid_for(slot, 256, 2048), (unsigned)slots), dim3(256), 0, (hipStream_t)stream, x,
+                     y, (uint32_t)slot, (uint32_t)cin, plain, dropout_threshold(rate), 1.f / (1.f - rate), seed0, stride);
+  return xv_launch_status();
+}
+
 // y[..., :Ca] = a, y[..., Ca:] = b over the whole padded buffers (tf.concat(axis=3), fusion_fcn.py:27-28)
 extern "C" int xv_concat_channels(const xv_act* a, const xv_act* b, const xv_act* y, void* stream) {
   XV_REQUIRE_BF16(a, b, y);
@@ -1812,6 +1965,65 @@ extern "C" int xv_mc_uncertainty_head_fwd(const float* S, const float* bias, int
     default: XV_UH(32); break;
   }
 #undef XV_UH
+  return xv_launch_status();
+}
+
+// Moments pass of the uncertainty-weighted Dirichlet fusion (see uncertainty_moments_kernel): Sa / Sb as xv_variance_head_fwd
+// takes them, [(T+1) n][hi+2][wi+2][CP] each.
+extern "C" int xv_uncertainty_moments(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                                      int wi, int num_classes, int num_samples, float* mvar, float* vmax, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && mvar && vmax && ((uintptr_t)vmax & 3) == 0);
+  XV_CHECK_SHAPE(num_classes >= 1 && num_classes <= 32 && num_samples >= 1 && num_samples <= 1024);
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi) && (int64_t)n * (num_samples + 1) < ((int64_t)1 << 31));
+  const int64_t npix = (int64_t)n * hi * wi * 64;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(vmax, 0, 2 * sizeof(float), s);
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid(grid_for(npix, 512, 256), 2);
+#define XV_UM(CMV)                                                                                                          \
+  hipLaunchKernelGGL(uncertainty_moments_kernel<CMV>, grid, dim3(512), 0, s, Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, \
+                     num_samples, mvar, reinterpret_cast<uint32_t*>(vmax))
+  switch ((num_classes + 3) / 4) {
+    case 1: XV_UM(4); break;
+    case 2: XV_UM(8); break;
+    case 3: XV_UM(12); break;
+    case 4: XV_UM(16); break;
+    case 5: XV_UM(20); break;
+    case 6: XV_UM(24); break;
+    case 7: XV_UM(28); break;
+    default: XV_UM(32); break;
+  }
+#undef XV_UM
+  return xv_launch_status();
+}
+
+// Fusion head of the uncertainty-weighted Dirichlet fusion (see uncertainty_dirichlet_head_kernel): params float [2][C][C]
+// with params[e][j][c] = A_e[j][c]; mvar / vmax from xv_uncertainty_moments.
+extern "C" int xv_uncertainty_dirichlet_head_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
+                                                 int hi, int wi, int num_classes, const float* mvar, const float* vmax,
+                                                 const float* params, const float* logprior, int64_t* label, float* fused_score,
+                                                 float* probs, float* mix, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && mvar && vmax && params && logprior && label);
+  XV_CHECK_SHAPE(num_classes >= 1 && num_classes <= 32 && xv_dims_sane(n, hi, wi));
+  const int64_t npix = (int64_t)n * hi * wi * 64;
+  XV_CHECK_SHAPE((npix + 255) / 256 <= 0x7fffffff);
+  const unsigned grid = (unsigned)((npix + 255) / 256);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_UDH(CMV)                                                                                                         \
+  hipLaunchKernelGGL(uncertainty_dirichlet_head_kernel<CMV>, dim3(grid), dim3(256),                                         \
+                     (size_t)(2 * num_classes * CMV + 3 * CMV) * 4, s, Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, mvar, \
+                     vmax, params, logprior, label, fused_score, probs, mix)
+  switch ((num_classes + 3) / 4) {
+    case 1: XV_UDH(4); break;
+    case 2: XV_UDH(8); break;
+    case 3: XV_UDH(12); break;
+    case 4: XV_UDH(16); break;
+    case 5: XV_UDH(20); break;
+    case 6: XV_UDH(24); break;
+    case 7: XV_UDH(28); break;
+    default: XV_UDH(32); break;
+  }
+#undef XV_UDH
   return xv_launch_status();
 }
 

@@ -267,6 +267,107 @@ __device__ static __forceinline__ int xv_mc_finish(const float (&mean)[CM], cons
   return bi;
 }
 
+// Uncertainty-weighted Dirichlet fusion (uncertainty_dirichlet_mix.py:18-52): per expert and pixel the fitted parameters are
+// softened towards the standard ones (ones plus the identity) by mix = mean_c variance / max variance,
+//   alpha[j][c] = A[j][c] (1 - mix) + mix (1 + delta_jc),
+//   ll[c] = sum_j (alpha[j][c] - 1) log(1e-20 + p[j] / sum p) + lgamma(sum_j alpha[j][c]) - sum_j lgamma(alpha[j][c]),
+// and score[c] = sum_e ll_e[c] + logprior[c].  The parameters differ per pixel, so the C^2 + C lgamma per expert are taken here
+// (ocml's lgammaf; its call sites stay ROLLED -- one copy per expert instead of C^2 -- while the dot products over j unroll on
+// statically indexed registers).  `A` is one expert's table in LDS, TRANSPOSED and padded with zeros: A[c * CM + j] = A[j][c];
+// `cs[c]` = sum_j A[j][c] rounded once from double: sum_j alpha[j][c] = cs[c] (1 - mix) + mix (C + 1) is linear in mix.
+// mix = 1 gives alpha = 1 + delta_jc exactly, whatever A holds; mix = 0 gives alpha = A exactly.  Renormalisation and logarithm
+// are those of dirichlet_fuse_kernel (xv_fast_rcp, xv_fast_log).  The fusion head (pointwise.hip) and
+// xv_uncertainty_dirichlet_fuse (fusion.hip) both run these functions: equal p, mvar and vmax give equal bits, for any CM >= C
+// (padding adds exact zeros); contraction is off inside them.  max variance 0 (identical samples everywhere; the reference
+// divides 0 / 0 there) gives mix = 0, the plain Dirichlet fusion.
+__device__ static __forceinline__ float xv_udm_mix(float mvar, float vmax) {
+#pragma clang fp contract(off)
+  return vmax > 0.f ? fminf(mvar / vmax, 1.f) : 0.f;
+}
+
+__device__ static __forceinline__ float xv_udm_alpha(float a, float om, float mix, bool diag) {
+  return __builtin_fmaf(a, om, diag ? mix + mix : mix);
+}
+
+template <int CM>
+__device__ static __forceinline__ void xv_udm_add(float (&total)[CM], const float (&p)[CM], float mix, const float* A,
+                                                   const float* cs, int C, bool first) {
+#pragma clang fp contract(off)
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < CM; ++k) sum = sum + p[k];
+  const float rs = xv_fast_rcp(sum);
+  float lx[CM];
+#pragma unroll
+  for (int k = 0; k < CM; ++k) lx[k] = k < C ? xv_fast_log(__builtin_fmaf(p[k], rs, 1e-20f)) : 0.f;
+  const float om = 1.f - mix;
+  const float top = mix * (float)(C + 1);
+#pragma unroll 1
+  for (int c = 0; c < C; ++c) {
+    const float* row = A + c * CM;
+    float dot = 0.f;
+#pragma unroll
+    for (int j = 0; j < CM; ++j) dot = __builtin_fmaf(xv_udm_alpha(row[j], om, mix, j == c) - 1.f, lx[j], dot);
+    float lg = 0.f;
+#pragma unroll 1
+    for (int j = 0; j < C; ++j) lg = lg + lgammaf(xv_udm_alpha(row[j], om, mix, j == c));
+    const float L = (dot + lgammaf(__builtin_fmaf(cs[c], om, top))) - lg;
+#pragma unroll
+    for (int cc = 0; cc < CM; ++cc)           // static register indexing: a select, not total[c] with a run-time c
+      if (cc == c) total[cc] = first ? L : total[cc] + L;
+  }
+}
+
+// total <- the fused score; returns its argmax over the first C classes (lowest index on ties, tf.argmax)
+template <int CM>
+__device__ static __forceinline__ int xv_udm_finish(float (&total)[CM], const float* lp, int C) {
+#pragma clang fp contract(off)
+  float best = 0.f;
+  int bi = 0;
+#pragma unroll
+  for (int c = 0; c < CM; ++c)
+    if (c < C) {
+      total[c] = total[c] + lp[c];
+      if (c == 0 || total[c] > best) best = total[c], bi = c;
+    }
+  return bi;
+}
+
+// One expert's [C][C] parameters (A[j][c], row-major over j) into the LDS table xv_udm_add reads: nthreads threads of a
+// workgroup; the caller synchronises afterwards.
+template <int CM>
+__device__ static __forceinline__ void xv_udm_stage(float* tab, float* cs, const float* __restrict__ A_g, int C, int tid,
+                                                     int nthreads) {
+  for (int i = tid; i < C * CM; i += nthreads) {
+    const int j = i % CM, c = i / CM;
+    tab[i] = j < C ? A_g[j * C + c] : 0.f;
+  }
+  for (int c = tid; c < CM; c += nthreads) {
+    double s = 0.0;
+    if (c < C)
+      for (int j = 0; j < C; ++j) s += (double)A_g[j * C + c];
+    cs[c] = (float)s;
+  }
+}
+
+// A workgroup's maximum of non-negative floats (they order like their bit patterns) into *dst with ONE atomic: registers,
+// then the wave (DPP-free shuffles), then LDS (`red`: one word per wave).  Every thread of the workgroup calls it.
+__device__ static __forceinline__ void xv_block_max_nonneg(float v, uint32_t* red, uint32_t* dst) {
+  uint32_t b = __builtin_bit_cast(uint32_t, v);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)b, off, 64);
+    b = o > b ? o : b;
+  }
+  const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  if ((threadIdx.x & 63) == 0) red[wave] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < nw; ++i) b = red[i] > b ? red[i] : b;
+    if (b) atomicMax(dst, b);
+  }
+}
+
 // Order-preserving map of packed bf16 bit patterns onto signed 16-bit integers (an involution: negative values have their
 // magnitude bits flipped), for a 2x2 max on packed pairs WITHOUT a preceding relu.
 __device__ static __forceinline__ uint32_t pk_ord_bf16(uint32_t x) {

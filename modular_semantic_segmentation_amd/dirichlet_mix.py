@@ -76,7 +76,7 @@ class DirichletFusion(BaseModel):
         BaseModel.__init__(self, name='DirichletFusion', output_dir=output_dir, custom_training=True,
                            **standard_config)
 
-    def _build_graph(self):
+    def _build_experts(self):
         engine_cls, init = expert_factory(self.config['expert_model'], self.config.get('conv_dtype', 'bf16'))
         if not hasattr(self, 'experts'):
             self.experts = {}
@@ -86,6 +86,9 @@ class DirichletFusion(BaseModel):
                                            seed=self.config.get('seed')))
                 self.experts[m] = engine_cls(m, cin, self.config['num_units'], self.config['num_classes'],
                                              self.variables, device=self.device, **engine_options(self.config))
+
+    def _build_graph(self):
+        self._build_experts()
         if hasattr(self, 'dirichlet_params'):
             am1, lognorm, logprior = dirichlet_tables([self.dirichlet_params[m] for m in self.modalities],
                                                       self.class_counts, self.config['class_prior'],

@@ -595,6 +595,39 @@ class FcnEngine(object):
         self._dropout_pass = p0 + T
         return S, (n, h // 8, w // 8)
 
+    def mc_input_scores(self, x, num_samples, rate, seed):
+        """The passes of the uncertainty-weighted Dirichlet fusion (uncertainty_dirichlet_mix.py:106-127): the plain pass and
+        `num_samples` passes on the INPUT with whole pixels dropped at `rate` (ops.dropout_pixels), as low-resolution class
+        scores float32 [(T+1) N][h/8+2][w/8+2][CP], slot-major (slot 0 the plain pass, slot t sample t).  The site is the
+        input, so nothing is shared between the passes: all T + 1 trunks run, the samples as batches of at most
+        mc_chunk_images images.  Sample t carries the bits of pass p0 + t-1 run alone, lowres_scores(dropout_pixels(x, rate,
+        _dropout_seed_of(seed, pass, 'input_drop'))) (p0: the engine's pass counter, which advances by T; masks are per sample,
+        so chunking changes no bit)."""
+        T = self._mc_check('mc_input_scores', num_samples)
+        n, h, w, _ = x.shape
+        x = x.contiguous()
+        cp = (self.C + 3) // 4 * 4
+        key = ('mci_S', T, n, h // 8, w // 8)
+        S = self._arena.get(key)
+        if S is None:
+            S = self._arena[key] = torch.zeros(((T + 1) * n, h // 8 + 2, w // 8 + 2, cp), dtype=torch.float32,
+                                               device=self.device)
+        p0 = self._dropout_pass
+        ops.score_lowres(self.encoder(x)['fused'], self.w['score'], self.C, S[:n])
+        per = max(1, int(self.mc_chunk_images) // n)               # samples per chunk
+        a = 0
+        while a < T:
+            k = min(per, T - a)
+            ykey = ('mci_x', k * n, h, w)
+            xs = self._arena.get(ykey)
+            if xs is None:
+                xs = self._arena[ykey] = torch.empty((k * n, h, w, self.cin), dtype=torch.float32, device=self.device)
+            ops.dropout_pixels_samples(x, k, rate, self._dropout_seed_of(seed, p0 + a, 'input_drop'), 1000003, plain=False, y=xs)
+            ops.score_lowres(self.encoder(xs)['fused'], self.w['score'], self.C, S[(1 + a) * n:(1 + a + k) * n])
+            a += k
+        self._dropout_pass = p0 + T
+        return S, (n, h // 8, w // 8)
+
     def _mc_check(self, who, num_samples):
         """What the batched samplers refuse; returns T"""
         if self.conv_dtype != 'bf16':

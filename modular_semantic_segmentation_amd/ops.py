@@ -667,6 +667,122 @@ def sampling_uncertainty(samples, want_label=True, want_mean=True, want_entropy=
     return out
 
 
+def dropout_pixels_samples(x, num_samples, rate, seed0, stride, plain=True, y=None):
+    """Input dropout of whole pixels (xv_dropout_pixels_samples): x float32 [n, h, w, cin] -> float32 [(plain + T) n, h, w,
+    cin], slot-major -- slot 0 = x when `plain`, sample t = 0 .. T-1 = dropout_pixels(x, rate, seed0 + t * stride)."""
+    _need(x, torch.float32, 'x')
+    if x.dim() != 4:
+        raise ValueError('x of shape [n, h, w, cin]')
+    T = int(num_samples)
+    n, h, w, cin = x.shape
+    shape = ((T + int(bool(plain))) * n, h, w, cin)
+    if y is None:
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _need(y, torch.float32, 'y')
+    if tuple(y.shape) != shape:
+        raise ValueError('y of shape %s, expected %s' % (tuple(y.shape), shape))
+    rc = _lib.lib().xv_dropout_pixels_samples(_ptr(x), n, h, w, cin, _ptr(y), T, int(bool(plain)), float(rate),
+                                             int(seed0) & 0xffffffffffffffff, int(stride) & 0xffffffffffffffff, _stream())
+    _lib.check(rc, 'xv_dropout_pixels_samples')
+    return y
+
+
+def dropout_pixels(x, rate, seed, y=None):
+    """tf.layers.dropout(x, rate, noise_shape=[N, H, W, 1], training=True) on the dense float32 input: one draw per pixel,
+    shared by its channels; kept pixels scaled by 1 / (1 - rate)."""
+    return dropout_pixels_samples(x, 1, rate, seed, 0, plain=False, y=y)
+
+
+def uncertainty_moments(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, num_samples):
+    """Both experts' low-resolution scores of (num_samples + 1) * n images each (slot 0 plain, then the samples) -> (mvar float32
+    [2, n, 8hi, 8wi]: the samples' population variance averaged over the classes, the bits of variance_head's 'variance'; vmax
+    float32 [2]: each expert's largest per-class variance over the whole call)."""
+    for t, name in ((Sa, 'Sa'), (Sb, 'Sb'), (bias_a, 'bias_a'), (bias_b, 'bias_b')):
+        _need(t, torch.float32, name)
+    T, C = int(num_samples), int(num_classes)
+    cp = (C + 3) // 4 * 4
+    for t in (Sa, Sb):
+        if tuple(t.shape) != ((T + 1) * n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores of shape %s, expected %s' % (tuple(t.shape), ((T + 1) * n, hi + 2, wi + 2, cp)))
+    mvar = torch.empty((2, n, 8 * hi, 8 * wi), dtype=torch.float32, device=Sa.device)
+    vmax = torch.empty(2, dtype=torch.float32, device=Sa.device)
+    rc = _lib.lib().xv_uncertainty_moments(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C, T, _ptr(mvar),
+                                          _ptr(vmax), _stream())
+    _lib.check(rc, 'xv_uncertainty_moments')
+    return mvar, vmax
+
+
+def uncertainty_dirichlet_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, mvar, vmax, params, logprior, want_score=False,
+                               want_probs=False, want_mix=False):
+    """The plain slots of both experts' low-resolution scores (any number of slots behind them), mvar / vmax of
+    uncertainty_moments, params float32 [2, C, C] (params[e, j, c]) and logprior float32 [C] -> dict 'label' (int64 [n, 8hi,
+    8wi]) and, where asked, 'fused_score' (float32 [n, 8hi, 8wi, C]), 'probs' (float32 [2, n, 8hi, 8wi, C]) and 'mix' (float32
+    [2, n, 8hi, 8wi])."""
+    for t, name in ((Sa, 'Sa'), (Sb, 'Sb'), (bias_a, 'bias_a'), (bias_b, 'bias_b'), (mvar, 'mvar'), (vmax, 'vmax'),
+                    (params, 'params'), (logprior, 'logprior')):
+        _need(t, torch.float32, name)
+    C = int(num_classes)
+    cp = (C + 3) // 4 * 4
+    for t in (Sa, Sb):
+        if t.dim() != 4 or t.shape[0] < n or tuple(t.shape[1:]) != (hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores of shape %s, expected at least %s' % (tuple(t.shape), (n, hi + 2, wi + 2, cp)))
+    dev, ho, wo = Sa.device, 8 * hi, 8 * wi
+    if tuple(mvar.shape) != (2, n, ho, wo) or vmax.numel() != 2 or tuple(params.shape) != (2, C, C) or logprior.numel() != C:
+        raise ValueError('mvar [2, n, 8hi, 8wi], vmax [2], params [2, C, C] and logprior [C]')
+    out = {'label': torch.empty((n, ho, wo), dtype=torch.int64, device=dev)}
+    if want_score:
+        out['fused_score'] = torch.empty((n, ho, wo, C), dtype=torch.float32, device=dev)
+    if want_probs:
+        out['probs'] = torch.empty((2, n, ho, wo, C), dtype=torch.float32, device=dev)
+    if want_mix:
+        out['mix'] = torch.empty((2, n, ho, wo), dtype=torch.float32, device=dev)
+    rc = _lib.lib().xv_uncertainty_dirichlet_head_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C, _ptr(mvar),
+                                                     _ptr(vmax), _ptr(params), _ptr(logprior), _ptr(out['label']),
+                                                     _ptr(out.get('fused_score')), _ptr(out.get('probs')), _ptr(out.get('mix')),
+                                                     _stream())
+    _lib.check(rc, 'xv_uncertainty_dirichlet_head_fwd')
+    return out
+
+
+def uncertainty_dirichlet_fuse(probs, mvar, vmax, params, logprior, want_score=True, want_label=True):
+    """uncertainty_dirichlet_mix.py:18-52 on two experts: probs float32 [..., C] each, mvar float32 [2, ...], vmax float32 [2],
+    params float32 [2, C, C], logprior float32 [C] -> (fused label int64 [...] or None, fused score float32 [..., C] or None)."""
+    for t, name in ((mvar, 'mvar'), (vmax, 'vmax'), (params, 'params'), (logprior, 'logprior')) + tuple((p, 'probs') for p in probs):
+        _need(t, torch.float32, name)
+    if len(probs) != 2:
+        raise ValueError('two experts')
+    c = probs[0].shape[-1]
+    shape = tuple(probs[0].shape[:-1])
+    if tuple(probs[1].shape) != shape + (c,) or tuple(mvar.shape) != (2,) + shape or vmax.numel() != 2 or \
+            tuple(params.shape) != (2, c, c) or logprior.numel() != c:
+        raise ValueError('probs [..., C] twice, mvar [2, ...], vmax [2], params [2, C, C] and logprior [C]')
+    dev = probs[0].device
+    fused = torch.empty(shape, dtype=torch.int64, device=dev) if want_label else None
+    score = torch.empty(shape + (c,), dtype=torch.float32, device=dev) if want_score else None
+    rc = _lib.lib().xv_uncertainty_dirichlet_fuse(_ptr_array(probs), _ptr(mvar), _ptr(vmax), _ptr(params), _ptr(logprior), c,
+                                                 probs[0].numel() // c, _ptr(fused), _ptr(score), _stream())
+    _lib.check(rc, 'xv_uncertainty_dirichlet_fuse')
+    return fused, score
+
+
+def uncertainty_weights(unc, mvar=None, vmax=None):
+    """One expert's per-class uncertainties float32 [..., C] (non-negative) -> (mvar float32 [...], their class mean; vmax
+    float32 [1], their maximum over everything).  mvar / vmax: views to write into (one expert's part of a [2, ...] pair)."""
+    _need(unc, torch.float32, 'unc')
+    c = unc.shape[-1]
+    if mvar is None:
+        mvar = torch.empty(tuple(unc.shape[:-1]), dtype=torch.float32, device=unc.device)
+    if vmax is None:
+        vmax = torch.empty(1, dtype=torch.float32, device=unc.device)
+    _need(mvar, torch.float32, 'mvar')
+    _need(vmax, torch.float32, 'vmax')
+    if mvar.numel() * c != unc.numel() or vmax.numel() != 1:
+        raise ValueError('mvar of one value per pixel and vmax of one value')
+    rc = _lib.lib().xv_uncertainty_weights(_ptr(unc), c, unc.numel() // c, _ptr(mvar), _ptr(vmax), _stream())
+    _lib.check(rc, 'xv_uncertainty_weights')
+    return mvar, vmax
+
+
 def softmax_argmax(score, want_prob=True, want_label=True):
     _need(score, torch.float32, 'score')
     c = score.shape[-1]
