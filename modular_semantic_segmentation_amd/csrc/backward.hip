@@ -8,14 +8,6 @@
 
 namespace {
 
-inline int grid_for(int64_t total, int per_block = 256, int cap = 8192) {
-  int64_t g = (total + per_block - 1) / per_block;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-__device__ inline float bf_lo(uint32_t w) { return bf16_bits_to_f32(w & 0xffffu); }
-__device__ inline float bf_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
 // ---- MaxPoolGrad + ReluGrad: dy[pos] = dpooled if pos is the (first) max of its 2x2 window and
 // y[pos] > 0, else 0  (max_pooling2d, simple_fcn.py:41,44,48,58 under the relu of the conv above) ----
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const __bf16* __restrict__ y, const __bf16* __restrict__ dp,
@@ -172,7 +164,7 @@ __global__ __launch_bounds__(1024) void count_valid_kernel(const int32_t* __rest
 }
 
 // ---- head backward (loss + gradients), in the same commuted form as the forward head ---------------
-// score = bilinear_x8(S) + bs with S = fused . Ws at 1/8 resolution (see pointwise.hip): the relu of the
+// score = bilinear_x8(S) + bs with S = fused . Ws at 1/8 resolution (see heads.hip): the relu of the
 // x8 deconv is the identity because fused >= 0, and wherever it is not strictly the identity (all four
 // source features of a channel are 0) the gradient entries that differ are zeroed again by the relu
 // masks of score_conv4 / upscore_conv5 further down, so the linear form gives the reference's gradients.
@@ -761,7 +753,7 @@ extern "C" int xv_maxpool2x2_bwd(const xv_act* y, const xv_act* dpooled, const x
   XV_CHECK_SHAPE(dy->n == y->n && dy->h == y->h && dy->w == y->w && dy->c == y->c);
   XV_CHECK_SHAPE(dpooled->n == y->n && dpooled->h == y->h / 2 && dpooled->w == y->w / 2 && dpooled->c == y->c);
   const int64_t total = (int64_t)y->n * (y->h / 2) * (y->w / 2) * (y->c >> 3);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(xv_grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                      (const __bf16*)y->data, (const __bf16*)dpooled->data, (__bf16*)dy->data, y->n, y->h / 2, y->w / 2, y->c);
   return xv_launch_status();
 }
@@ -772,7 +764,7 @@ extern "C" int xv_relu_bwd(const xv_act* g, const xv_act* ref, const xv_act* out
   XV_CHECK_SHAPE(g->n == ref->n && g->h == ref->h && g->w == ref->w && g->c == ref->c && (g->c & 7) == 0);
   XV_CHECK_SHAPE(out->n == g->n && out->h == g->h && out->w == g->w && out->c == g->c);
   const int64_t n8 = (int64_t)g->n * (g->h + 2) * (g->w + 2) * g->c / 8;
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n8)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)g->data,
+  hipLaunchKernelGGL(relu_bwd_kernel, dim3(xv_grid_for(n8)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)g->data,
                      (const __bf16*)ref->data, (__bf16*)out->data, n8);
   return xv_launch_status();
 }
@@ -784,7 +776,7 @@ extern "C" int xv_upsample2x_bwd(const xv_act* dfused, const xv_act* s5, const x
                  dfused->c == s5->c);
   XV_CHECK_SHAPE(ds5->n == s5->n && ds5->h == s5->h && ds5->w == s5->w && ds5->c == s5->c);
   const int64_t total = (int64_t)s5->n * s5->h * s5->w * (s5->c >> 3);
-  hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(xv_grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                      (const __bf16*)dfused->data, (const __bf16*)s5->data, (__bf16*)ds5->data, s5->n, s5->h, s5->w, s5->c);
   return xv_launch_status();
 }
@@ -794,7 +786,7 @@ extern "C" int xv_count_valid_labels(const int32_t* labels, int num_classes, int
   XV_CHECK_SHAPE(npix > 0 && num_classes >= 1);
   // one 1 024-thread workgroup per CU: sixteen waves' loads in flight per CU, and one same-address 64-bit atomic per workgroup
   // (1 024 workgroups of 256 threads: 19 us for the 19 MB label map of 16 images; 256 of 256: 15 us)
-  hipLaunchKernelGGL(count_valid_kernel, dim3(grid_for(npix, 1024, 256)), dim3(1024), 0, (hipStream_t)stream, labels,
+  hipLaunchKernelGGL(count_valid_kernel, dim3(xv_grid_for(npix, 1024, 256)), dim3(1024), 0, (hipStream_t)stream, labels,
                      num_classes, npix, reinterpret_cast<unsigned long long*>(count));
   return xv_launch_status();
 }
@@ -861,16 +853,7 @@ extern "C" int xv_decoder_head_bwd(const xv_act* fused, const float* w_score, co
     hipLaunchKernelGGL(head_dws_reduce_kernel, dim3((U * CMV + 15) / 16), dim3(256), 0, s, (const float*)dws_part,    \
                        (int)g2, U, CMV, num_classes, dw_score);                                                       \
   }
-  switch (CM / 4) {
-    case 1: XV_HB(4) break;
-    case 2: XV_HB(8) break;
-    case 3: XV_HB(12) break;
-    case 4: XV_HB(16) break;
-    case 5: XV_HB(20) break;
-    case 6: XV_HB(24) break;
-    case 7: XV_HB(28) break;
-    default: XV_HB(32) break;
-  }
+  XV_CM_SWITCH(num_classes, XV_HB)
 #undef XV_HB
   return xv_launch_status();
 }
@@ -979,7 +962,7 @@ extern "C" int xv_adam_step(float* param, const float* grad, float* m, float* v,
                             float beta2, float eps, float grad_scale, void* stream) {
   XV_CHECK_ARG(param && grad && m && v);
   XV_CHECK_SHAPE(n > 0);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, n, lr_t, beta1,
+  hipLaunchKernelGGL(adam_kernel, dim3(xv_grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, n, lr_t, beta1,
                      beta2, eps, grad_scale);
   return xv_launch_status();
 }
@@ -988,7 +971,7 @@ extern "C" int xv_rmsprop_step(float* param, const float* grad, float* ms, int64
                                float grad_scale, void* stream) {
   XV_CHECK_ARG(param && grad && ms);
   XV_CHECK_SHAPE(n > 0);
-  hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, ms, n, lr, decay,
+  hipLaunchKernelGGL(rmsprop_kernel, dim3(xv_grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, ms, n, lr, decay,
                      eps, grad_scale);
   return xv_launch_status();
 }
@@ -997,7 +980,7 @@ extern "C" int xv_adagrad_step(float* param, const float* grad, float* accum, in
                                void* stream) {
   XV_CHECK_ARG(param && grad && accum);
   XV_CHECK_SHAPE(n > 0);
-  hipLaunchKernelGGL(adagrad_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, accum, n, lr,
+  hipLaunchKernelGGL(adagrad_kernel, dim3(xv_grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, accum, n, lr,
                      grad_scale);
   return xv_launch_status();
 }

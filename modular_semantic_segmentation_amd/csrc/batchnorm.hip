@@ -13,13 +13,7 @@
 
 namespace {
 
-__device__ __forceinline__ float bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
-
-inline int bn_grid(int64_t total, int cap = 2048) {
-  int64_t g = (total + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+inline int bn_grid(int64_t total, int cap = 2048) { return xv_grid_for(total, 256, cap); }
 
 // ---- per-channel sums over the interior of a padded-NHWC bf16 tensor ----------------------------------------
 // weight of source pixel i in output pixel o of the bilinear x S transposed conv (0 if not a tap; custom_layers.py:8-25)
@@ -1468,15 +1462,12 @@ __global__ __launch_bounds__(256) void score_dense_dgrad_kernel(const float* __r
 //   gradient du[px][u] = sum_c ds[px][c] W[u][c] in exact fp32 on v_mfma_f32_16x16x4_f32 (K = 4 classes per step).
 typedef __attribute__((ext_vector_type(4))) float sd_f32x4;
 
+// split3_bf16x8 (xv_common.h) with the halves packed by shift and mask: the form these two kernels were compiled from (the
+// v_perm_b32 of hi16_pair gives them other instructions)
 __device__ __forceinline__ void sd_split3(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
   uint32_t hh[8], mm[8], ll[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    hh[e] = __builtin_bit_cast(uint32_t, v[e]) & 0xffff0000u;
-    const float r1 = v[e] - __builtin_bit_cast(float, hh[e]);  // exact
-    mm[e] = __builtin_bit_cast(uint32_t, r1) & 0xffff0000u;
-    ll[e] = __builtin_bit_cast(uint32_t, r1 - __builtin_bit_cast(float, mm[e]));  // exact, fits 8 bits
-  }
+  for (int e = 0; e < 8; ++e) split3_bf16(v[e], hh[e], mm[e], ll[e]);
   auto pk = [](const uint32_t (&a)[8]) {
     return __builtin_bit_cast(bf16x8, u32x4{(a[0] >> 16) | (a[1] & 0xffff0000u), (a[2] >> 16) | (a[3] & 0xffff0000u),
                                             (a[4] >> 16) | (a[5] & 0xffff0000u), (a[6] >> 16) | (a[7] & 0xffff0000u)});
@@ -2288,18 +2279,6 @@ extern "C" int xv_upsample_raw_bwd_ws(const xv_act* dy, int factor, const xv_act
                      s, (const float*)workspace, (__bf16*)dx->data, dx->n, dx->h, dx->w, dx->c);
   return xv_launch_status();
 }
-
-#define XV_CM_SWITCH(C_, CALL) \
-  switch (((C_) + 3) / 4) {    \
-    case 1: CALL(4); break;    \
-    case 2: CALL(8); break;    \
-    case 3: CALL(12); break;   \
-    case 4: CALL(16); break;   \
-    case 5: CALL(20); break;   \
-    case 6: CALL(24); break;   \
-    case 7: CALL(28); break;   \
-    default: CALL(32); break;  \
-  }
 
 extern "C" int xv_score_dense_fwd(const xv_act* u, const float* w_score, const float* b_score, int num_classes,
                                   float* score, void* stream) {

@@ -13,7 +13,7 @@
 //   * Tile = 16x32 output pixels of conv1_2 x 64 channels, 8 waves, persistent workgroups over XCD-contiguous tile ranges,
 //     150 KB of LDS: two patch buffers (conv1_1 channels 0-31 / 32-63 of the 18x34 halo patch: conv1_2's two 32-channel
 //     chunks) + conv1_2's weights for both chunks (loaded once per workgroup by LDS-DMA).
-//   * Phase A (conv1_1): the arithmetic of conv_first_mfma_kernel (pointwise.hip), bit for bit -- every fp32 operand split
+//   * Phase A (conv1_1): the arithmetic of conv_first_mfma_kernel (conv_first.hip), bit for bit -- every fp32 operand split
 //     exactly into three bf16 terms, K = 9 cin (+ the bias against a constant 1) in ONE v_mfma_f32_16x16x32_bf16 step, six
 //     products in the same order -- on blocks of 16 consecutive patch pixels (39 blocks, wave w takes w, w + 8, ...), each
 //     lane gathering its own pixel's taps (the patch rows are 34 pixels long: a block straddles rows).  Patch pixels outside
@@ -74,41 +74,6 @@ static_assert(F1::lds_bytes(3) <= 160 * 1024, "does not fit the LDS");
 
 __device__ __forceinline__ int f1_swz(int row, int slot) { return slot ^ ((row >> 1) & 2); }  // = g4_swz16
 
-// the k-slot map of conv_first_mfma_kernel (pointwise.hip first_k_map): k-group g < 3 = window row g in memory order (the
-// first 8 of its 3 x CIN floats), group 3 = the leftovers (last channel of column 2 of the three rows) + the bias slot
-template <int CIN>
-__device__ __forceinline__ bool f1_k_map(int g, int e, int& dy, int& dx, int& ci) {
-  if (CIN == 3) {
-    if (g < 3) {
-      dy = g, dx = e / 3, ci = e % 3;
-      return true;
-    }
-    dy = e, dx = 2, ci = 2;
-    return e < 3;
-  }
-  dy = g, dx = e, ci = 0;  // CIN == 1
-  return g < 3 && e < 3;
-}
-
-// v = h + m + l exactly, each term a bf16 (as fp32 bit patterns with zero low halves)
-__device__ __forceinline__ void f1_split3(float v, uint32_t& h, uint32_t& m, uint32_t& l) {
-  h = __builtin_bit_cast(uint32_t, v) & 0xffff0000u;
-  const float r1 = v - __builtin_bit_cast(float, h);  // exact
-  m = __builtin_bit_cast(uint32_t, r1) & 0xffff0000u;
-  l = __builtin_bit_cast(uint32_t, r1 - __builtin_bit_cast(float, m));  // exact, fits 8 bits
-}
-__device__ __forceinline__ uint32_t f1_hi16_pair(uint32_t a, uint32_t b) {  // (a >> 16) | (b & 0xffff0000): v_perm_b32
-  return __builtin_amdgcn_perm(b, a, 0x07060302u);
-}
-__device__ __forceinline__ void f1_split3x8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-  uint32_t hh[8], mm[8], ll[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f1_split3(v[e], hh[e], mm[e], ll[e]);
-  h = __builtin_bit_cast(bf16x8, u32x4{f1_hi16_pair(hh[0], hh[1]), f1_hi16_pair(hh[2], hh[3]), f1_hi16_pair(hh[4], hh[5]), f1_hi16_pair(hh[6], hh[7])});
-  m = __builtin_bit_cast(bf16x8, u32x4{f1_hi16_pair(mm[0], mm[1]), f1_hi16_pair(mm[2], mm[3]), f1_hi16_pair(mm[4], mm[5]), f1_hi16_pair(mm[6], mm[7])});
-  l = __builtin_bit_cast(bf16x8, u32x4{f1_hi16_pair(ll[0], ll[1]), f1_hi16_pair(ll[2], ll[3]), f1_hi16_pair(ll[4], ll[5]), f1_hi16_pair(ll[6], ll[7])});
-}
-
 // OF8: y / pooled are e4m3 maps (value * out_mul, saturating): the first e4m3 map of the fp8 graph (fcn.fp8_plan), with the
 // epilogue of generation 4's <bf16 in, e4m3 out> form -- the same bytes as xv_conv2d_first_fwd + xv_conv2d_fwd onto e4m3 maps
 template <int CIN, bool OF8 = false>
@@ -159,11 +124,11 @@ __global__ __launch_bounds__(512, 2) void conv_first_pair_kernel(F1Args a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       int dy, dx, ci;
-      const bool ok = f1_k_map<CIN>(g, e, dy, dx, ci);
+      const bool ok = first_k_map<CIN>(g, e, dy, dx, ci);
       wv[e] = ok ? a.w1[((dy * 3 + dx) * CIN + ci) * 64 + jb * 16 + n15] : 0.f;
       if (e == BIAS_E) wv[e] = g == 3 ? a.b1[jb * 16 + n15] : wv[e];
     }
-    f1_split3x8(wv, wh[jb], wm[jb], wl[jb]);
+    split3_bf16x8(wv, wh[jb], wm[jb], wl[jb]);
   }
   // conv1_2's bias as four accumulator-shaped registers (lane's channels 16 g + 4 j + q: weight row 16 j + 4 g + q)
   f32x4 bvec[4];
@@ -325,12 +290,12 @@ __global__ __launch_bounds__(512, 2) void conv_first_pair_kernel(F1Args a) {
         const bool exact8 = __builtin_amdgcn_ballot_w64((lowbits & 0xffffu) != 0) == 0;
         bf16x8 xh, xm, xl;
         if (exact8) {
-          xh = __builtin_bit_cast(bf16x8, u32x4{f1_hi16_pair(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1])),
-                                                f1_hi16_pair(__builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])),
-                                                f1_hi16_pair(__builtin_bit_cast(uint32_t, v[4]), __builtin_bit_cast(uint32_t, v[5])),
-                                                f1_hi16_pair(__builtin_bit_cast(uint32_t, v[6]), __builtin_bit_cast(uint32_t, v[7]))});
+          xh = __builtin_bit_cast(bf16x8, u32x4{hi16_pair(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1])),
+                                                hi16_pair(__builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])),
+                                                hi16_pair(__builtin_bit_cast(uint32_t, v[4]), __builtin_bit_cast(uint32_t, v[5])),
+                                                hi16_pair(__builtin_bit_cast(uint32_t, v[6]), __builtin_bit_cast(uint32_t, v[7]))});
         } else {
-          f1_split3x8(v, xh, xm, xl);
+          split3_bf16x8(v, xh, xm, xl);
         }
         const int p = pcur, hx = hxcur;
         if (blk + C::NWAVES < C::NBLK) request(fast, blk + C::NWAVES, n, y0, x0);  // next block's taps land behind this block's MFMAs

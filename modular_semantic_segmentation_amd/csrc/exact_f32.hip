@@ -512,10 +512,7 @@ __global__ __launch_bounds__(256) void score_lowres_f32_kernel(const float* __re
   }
 }
 
-inline unsigned f32_grid(int64_t total) {
-  int64_t g = (total + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 65535 ? 65535 : g));
-}
+inline unsigned f32_grid(int64_t total) { return (unsigned)xv_grid_for(total, 256, 65535); }
 
 }  // namespace
 

@@ -41,11 +41,6 @@ __device__ static __forceinline__ void load_row(const float* __restrict__ p, int
   }
 }
 
-inline int grid_for(int64_t total, int per_block = 256, int cap = 8192) {
-  int64_t g = (total + per_block - 1) / per_block;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 // bayes_mix.py:12-58 + :161.  score[c] = (ll_0[c] + ll_1[c] + ...) + logprior[c]; argmax, first index on ties.
 template <int CMAX>
 __global__ __launch_bounds__(256) void bayes_fuse_kernel(LabelPtrs labels, int E, const float* __restrict__ loglik,
@@ -205,7 +200,7 @@ __global__ __launch_bounds__(256) void dirichlet_fuse_kernel(ProbPtrs probs, int
       } else {
         for (int c = 0; c < C; ++c) {
           const float* row = tab + ((int64_t)e * C + c) * CMAX;
-          // explicit fmaf chain: the fused two-expert head (pointwise.hip fused_head_kernel) repeats this arithmetic and
+          // explicit fmaf chain: the fused two-expert head (heads.hip fused_head_kernel) repeats this arithmetic and
           // must produce the same bits, so nothing is left to the compiler's contraction choices
           float dot = 0.f;
 #pragma unroll
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(256) void dirichlet_fuse_kernel(ProbPtrs probs, int
 // 116 AGPRs, one wave per SIMD: 161 us).  16 images of 768x384 (tools/dirichlet_head_ab.py): scalar form 108-117 us (0.52-0.57
 // of 8 TB/s, bound by its 288 scalar FMAs and their index arithmetic), this one 87 us (0.70; 5.65 TB/s of the 6.29 TB/s a
 // float4 copy reaches); two / four pixels per thread sharing the table rows read from LDS: 89 / 92 us -- the rows are not
-// what binds this kernel once the FMAs are packed, unlike the fused head (pointwise.hip).
+// what binds this kernel once the FMAs are packed, unlike the fused head (heads.hip).
 template <int CM>
 __global__ __launch_bounds__(256) void dirichlet_fuse_pk_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
                                                                const float* __restrict__ am1, const float* __restrict__ lognorm,
@@ -353,7 +348,7 @@ __global__ __launch_bounds__(256) void average_fuse_kernel(ProbPtrs probs, int E
 }
 
 // variance_mix.py:7-15 (variance_fusion): the certainty-weighted mean of the experts' probabilities, certainty = 1 / (1e-20 +
-// variance) per expert and pixel, and its argmax -- the fusion step of the variance head (pointwise.hip) through the same device
+// variance) per expert and pixel, and its argmax -- the fusion step of the variance head (heads.hip) through the same device
 // functions (xv_common.h), so that the head's own probabilities and variances fed in here give its labels bit for bit.
 template <int CMAX>
 __global__ __launch_bounds__(256) void variance_fuse_kernel(ProbPtrs probs, ProbPtrs vars, int E, int C, int64_t npix,
@@ -377,7 +372,7 @@ __global__ __launch_bounds__(256) void variance_fuse_kernel(ProbPtrs probs, Prob
 
 // bayesian_fcn.py:48-57 (sampling_uncertainty) on MATERIALISED samples [T][npix][C]: mean over the samples and its argmax,
 // normed entropy of the mean, mean normed entropy of the samples, class-summed population variance -- the reduction of the
-// uncertainty head (pointwise.hip, mc_uncertainty_head_kernel) through the same device functions (xv_common.h), samples in the
+// uncertainty head (heads.hip, mc_uncertainty_head_kernel) through the same device functions (xv_common.h), samples in the
 // same order, so that the head's own p_t fed in here give its outputs bit for bit.
 template <int CMAX>
 __global__ __launch_bounds__(256) void sampling_uncertainty_kernel(const float* __restrict__ samples, int T, int C, int64_t npix,
@@ -410,7 +405,7 @@ __global__ __launch_bounds__(256) void sampling_uncertainty_kernel(const float* 
 
 // uncertainty_dirichlet_mix.py:18-52 on MATERIALISED tensors of two experts: probabilities [npix][C] each, mvar [2][npix] (the
 // class mean of each expert's uncertainty) and vmax [2] (its maximum) -> the fused score and its argmax -- the per-pixel step
-// of the fusion head (pointwise.hip, uncertainty_dirichlet_head_kernel) through the same device functions (xv_common.h), so
+// of the fusion head (heads.hip, uncertainty_dirichlet_head_kernel) through the same device functions (xv_common.h), so
 // that the head's own probabilities, mvar and vmax fed in here give its scores and labels bit for bit.  One pixel per thread,
 // tables in LDS.
 template <int CM>
@@ -601,7 +596,7 @@ __global__ __launch_bounds__(256) void narrow_labels_kernel(const int64_t* __res
 extern "C" int xv_narrow_labels(const int64_t* labels, int64_t n, uint8_t* out, void* stream) {
   XV_CHECK_ARG(labels && out && ((uintptr_t)labels & 15) == 0 && ((uintptr_t)out & 7) == 0);
   XV_CHECK_SHAPE(n > 0);
-  hipLaunchKernelGGL(narrow_labels_kernel, dim3(grid_for((n + 7) / 8, 256, 2048)), dim3(256), 0, (hipStream_t)stream, labels, out, n);
+  hipLaunchKernelGGL(narrow_labels_kernel, dim3(xv_grid_for((n + 7) / 8, 256, 2048)), dim3(256), 0, (hipStream_t)stream, labels, out, n);
   return xv_launch_status();
 }
 
@@ -618,16 +613,16 @@ extern "C" int xv_bayes_fuse(const int64_t* const* labels, int num_experts, cons
   const int cm = num_classes <= 16 ? 16 : 32;
   const size_t lds = (size_t)(num_experts * num_classes * cm + cm) * 4;
   if (num_experts == 2 && score_out == nullptr && (((uintptr_t)labels[0] | (uintptr_t)labels[1] | (uintptr_t)fused) & 15) == 0) {
-    hipLaunchKernelGGL(bayes_fuse2_kernel<32>, dim3(grid_for((npix + 1) / 2, 256, xv_num_cus() * 8)), dim3(256),
+    hipLaunchKernelGGL(bayes_fuse2_kernel<32>, dim3(xv_grid_for((npix + 1) / 2, 256, xv_num_cus() * 8)), dim3(256),
                        (size_t)(3 * num_classes * num_classes + num_classes) * 4, s, labels[0], labels[1], loglik, logprior,
                        num_classes, npix, fused);
     return xv_launch_status();
   }
   if (cm == 16)
-    hipLaunchKernelGGL(bayes_fuse_kernel<16>, dim3(grid_for(npix)), dim3(256), lds, s, lp, num_experts, loglik, logprior,
+    hipLaunchKernelGGL(bayes_fuse_kernel<16>, dim3(xv_grid_for(npix)), dim3(256), lds, s, lp, num_experts, loglik, logprior,
                        num_classes, npix, fused, score_out);
   else
-    hipLaunchKernelGGL(bayes_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), lds, s, lp, num_experts, loglik, logprior,
+    hipLaunchKernelGGL(bayes_fuse_kernel<32>, dim3(xv_grid_for(npix)), dim3(256), lds, s, lp, num_experts, loglik, logprior,
                        num_classes, npix, fused, score_out);
   return xv_launch_status();
 }
@@ -636,7 +631,7 @@ extern "C" int xv_bayes_fuse_lut(const int64_t* label_a, const int64_t* label_b,
                                  int64_t npix, int64_t* fused, void* stream) {
   XV_CHECK_ARG(label_a && label_b && lut && fused);
   XV_CHECK_SHAPE(num_classes >= 1 && num_classes <= 64 && npix > 0);
-  hipLaunchKernelGGL(bayes_lut_kernel, dim3(grid_for(npix)), dim3(256), (size_t)num_classes * num_classes * 4,
+  hipLaunchKernelGGL(bayes_lut_kernel, dim3(xv_grid_for(npix)), dim3(256), (size_t)num_classes * num_classes * 4,
                      (hipStream_t)stream, label_a, label_b, lut, num_classes, npix, fused);
   return xv_launch_status();
 }
@@ -666,14 +661,14 @@ extern "C" int xv_dirichlet_fuse(const float* const* probs, int num_experts, con
                        (size_t)(2 * 12 * 12 + 2 * 12 + 12) * 4, s, pp.p[0], pp.p[1], am1, lognorm, logprior, npix, fused,
                        score_out);
   else if (num_classes == 12 && vec)
-    hipLaunchKernelGGL((dirichlet_fuse_kernel<12, true>), dim3(grid_for(npix, 256, xv_num_cus() * 8)), dim3(256),
+    hipLaunchKernelGGL((dirichlet_fuse_kernel<12, true>), dim3(xv_grid_for(npix, 256, xv_num_cus() * 8)), dim3(256),
                        (size_t)(num_experts * 12 * 12 + num_experts * 12 + 12) * 4, s, pp, num_experts, am1, lognorm, logprior,
                        num_classes, npix, fused, score_out, vec);
   else if (cm == 16)
-    hipLaunchKernelGGL(dirichlet_fuse_kernel<16>, dim3(grid_for(npix)), dim3(256), lds, s, pp, num_experts, am1, lognorm,
+    hipLaunchKernelGGL(dirichlet_fuse_kernel<16>, dim3(xv_grid_for(npix)), dim3(256), lds, s, pp, num_experts, am1, lognorm,
                        logprior, num_classes, npix, fused, score_out, vec);
   else
-    hipLaunchKernelGGL(dirichlet_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), lds, s, pp, num_experts, am1, lognorm,
+    hipLaunchKernelGGL(dirichlet_fuse_kernel<32>, dim3(xv_grid_for(npix)), dim3(256), lds, s, pp, num_experts, am1, lognorm,
                        logprior, num_classes, npix, fused, score_out, vec);
   return xv_launch_status();
 }
@@ -691,10 +686,10 @@ extern "C" int xv_average_fuse(const float* const* probs, int num_experts, int n
   int vec = (num_classes & 3) == 0;
   for (int e = 0; e < num_experts; ++e) vec = vec && ((uintptr_t)probs[e] & 15) == 0;
   if (num_classes <= 16)
-    hipLaunchKernelGGL(average_fuse_kernel<16>, dim3(grid_for(npix)), dim3(256), 0, s, pp, num_experts, num_classes, npix,
+    hipLaunchKernelGGL(average_fuse_kernel<16>, dim3(xv_grid_for(npix)), dim3(256), 0, s, pp, num_experts, num_classes, npix,
                        fused, vec);
   else
-    hipLaunchKernelGGL(average_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, pp, num_experts, num_classes, npix,
+    hipLaunchKernelGGL(average_fuse_kernel<32>, dim3(xv_grid_for(npix)), dim3(256), 0, s, pp, num_experts, num_classes, npix,
                        fused, vec);
   return xv_launch_status();
 }
@@ -713,10 +708,10 @@ extern "C" int xv_variance_fuse(const float* const* probs, const float* const* v
   int vec = (num_classes & 3) == 0;
   for (int e = 0; e < num_experts; ++e) vec = vec && ((uintptr_t)probs[e] & 15) == 0;
   if (num_classes <= 16)
-    hipLaunchKernelGGL(variance_fuse_kernel<16>, dim3(grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
+    hipLaunchKernelGGL(variance_fuse_kernel<16>, dim3(xv_grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
                        npix, fused, fused_score, vec);
   else
-    hipLaunchKernelGGL(variance_fuse_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
+    hipLaunchKernelGGL(variance_fuse_kernel<32>, dim3(xv_grid_for(npix)), dim3(256), 0, s, pp, vp, num_experts, num_classes,
                        npix, fused, fused_score, vec);
   return xv_launch_status();
 }
@@ -730,10 +725,10 @@ extern "C" int xv_sampling_uncertainty(const float* samples, int num_samples, in
   const float ln_c = xv_ln_classes(num_classes);
   hipStream_t s = (hipStream_t)stream;
   if (num_classes <= 16)
-    hipLaunchKernelGGL(sampling_uncertainty_kernel<16>, dim3(grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
+    hipLaunchKernelGGL(sampling_uncertainty_kernel<16>, dim3(xv_grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
                        npix, ln_c, label, mean_prob, entropy, cond_entropy, variance, vec);
   else
-    hipLaunchKernelGGL(sampling_uncertainty_kernel<32>, dim3(grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
+    hipLaunchKernelGGL(sampling_uncertainty_kernel<32>, dim3(xv_grid_for(npix)), dim3(256), 0, s, samples, num_samples, num_classes,
                        npix, ln_c, label, mean_prob, entropy, cond_entropy, variance, vec);
   return xv_launch_status();
 }
@@ -750,16 +745,7 @@ extern "C" int xv_uncertainty_dirichlet_fuse(const float* const* probs, const fl
   hipLaunchKernelGGL(uncertainty_dirichlet_fuse_kernel<CMV>, dim3(grid), dim3(256),                                        \
                      (size_t)(2 * num_classes * CMV + 3 * CMV) * 4, s, probs[0], probs[1], mvar, vmax, params, logprior,    \
                      num_classes, npix, fused, fused_score, vec)
-  switch ((num_classes + 3) / 4) {
-    case 1: XV_UDF(4); break;
-    case 2: XV_UDF(8); break;
-    case 3: XV_UDF(12); break;
-    case 4: XV_UDF(16); break;
-    case 5: XV_UDF(20); break;
-    case 6: XV_UDF(24); break;
-    case 7: XV_UDF(28); break;
-    default: XV_UDF(32); break;
-  }
+  XV_CM_SWITCH(num_classes, XV_UDF)
 #undef XV_UDF
   return xv_launch_status();
 }
@@ -774,10 +760,10 @@ extern "C" int xv_uncertainty_weights(const float* uncertainty, int num_classes,
   const int vec = (num_classes & 3) == 0 && ((uintptr_t)uncertainty & 15) == 0;
   const float inv_c = 1.f / (float)num_classes;
   if (num_classes <= 16)
-    hipLaunchKernelGGL(uncertainty_weights_kernel<16>, dim3(grid_for(npix, 256, 512)), dim3(256), 0, s, uncertainty, num_classes,
+    hipLaunchKernelGGL(uncertainty_weights_kernel<16>, dim3(xv_grid_for(npix, 256, 512)), dim3(256), 0, s, uncertainty, num_classes,
                        npix, inv_c, mvar, reinterpret_cast<uint32_t*>(vmax), vec);
   else
-    hipLaunchKernelGGL(uncertainty_weights_kernel<32>, dim3(grid_for(npix, 256, 512)), dim3(256), 0, s, uncertainty, num_classes,
+    hipLaunchKernelGGL(uncertainty_weights_kernel<32>, dim3(xv_grid_for(npix, 256, 512)), dim3(256), 0, s, uncertainty, num_classes,
                        npix, inv_c, mvar, reinterpret_cast<uint32_t*>(vmax), vec);
   return xv_launch_status();
 }
@@ -792,7 +778,7 @@ extern "C" int xv_dirichlet_suffstats(const float* prob, const int32_t* labels, 
   const int vec = (num_classes & 3) == 0 && num_classes <= 32 && ((uintptr_t)prob & 15) == 0;
   // few workgroups: each ends with C*C same-address double atomics, which serialise across the chip (~12 ns each)
   // one 16-wave workgroup per CU
-  hipLaunchKernelGGL(suffstats_kernel, dim3(grid_for(npix, 1024, xv_num_cus())), dim3(1024), lds, (hipStream_t)stream,
+  hipLaunchKernelGGL(suffstats_kernel, dim3(xv_grid_for(npix, 1024, xv_num_cus())), dim3(1024), lds, (hipStream_t)stream,
                      prob, labels, num_classes, npix, S, reinterpret_cast<unsigned long long*>(counts), rep, vec);
   return xv_launch_status();
 }
@@ -805,7 +791,7 @@ extern "C" int xv_confusion_matrix(const int32_t* labels, const int64_t* pred, i
   const size_t lds = (size_t)num_classes * num_classes * rep * 4;        // 18 KB at C = 12
   const int vec = ((uintptr_t)labels & 15) == 0 && ((uintptr_t)pred & 15) == 0;
   // one 16-wave workgroup per CU: each ends with C*C same-address atomics, which serialise across the chip (~12 ns each)
-  hipLaunchKernelGGL(confusion_kernel, dim3(grid_for((npix + 7) / 8, 1024, xv_num_cus())), dim3(1024), lds,
+  hipLaunchKernelGGL(confusion_kernel, dim3(xv_grid_for((npix + 7) / 8, 1024, xv_num_cus())), dim3(1024), lds,
                      (hipStream_t)stream, labels, pred, num_classes, npix, reinterpret_cast<unsigned long long*>(cm), rep, vec);
   return xv_launch_status();
 }

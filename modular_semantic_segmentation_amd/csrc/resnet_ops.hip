@@ -16,10 +16,7 @@
 
 namespace {
 
-inline int rn_grid(int64_t total, int cap = 8192) {
-  int64_t g = (total + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+inline int rn_grid(int64_t total, int cap = 8192) { return xv_grid_for(total, 256, cap); }
 
 __global__ __launch_bounds__(256) void subsample2_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int N,
                                                         int Ho, int Wo, int c8) {

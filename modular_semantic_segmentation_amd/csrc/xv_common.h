@@ -41,6 +41,26 @@ static inline int xv_launch_status() {
   return e == hipSuccess ? XV_OK : (int)e;
 }
 
+// blocks of a grid-stride launch over `total` items: one block per `per_block` items, at least one, at most `cap`
+static inline int xv_grid_for(int64_t total, int per_block = 256, int cap = 8192) {
+  int64_t g = (total + per_block - 1) / per_block;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// Launchers of kernels templated on the padded class count CM (a multiple of 4, at most 32): CALL(CM) for the smallest CM that
+// holds C_ classes.  CALL is a statement or a block.
+#define XV_CM_SWITCH(C_, CALL) \
+  switch (((C_) + 3) / 4) {    \
+    case 1: CALL(4); break;    \
+    case 2: CALL(8); break;    \
+    case 3: CALL(12); break;   \
+    case 4: CALL(16); break;   \
+    case 5: CALL(20); break;   \
+    case 6: CALL(24); break;   \
+    case 7: CALL(28); break;   \
+    default: CALL(32); break;  \
+  }
+
 // Per-device caches (one process normally drives one GPU, but nothing here may depend on it): up to XV_MAX_DEVICES devices
 // of one process; an out-of-range device index falls back to querying every time.
 #define XV_MAX_DEVICES 16
@@ -135,6 +155,63 @@ __device__ static inline float bf16_bits_to_f32(uint32_t bits16) {
   return __builtin_bit_cast(float, bits16 << 16);
 }
 
+// the two bf16 halves of a packed word as fp32
+__device__ static __forceinline__ float bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
+__device__ static __forceinline__ float bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
+
+// Bilinear transposed-conv taps ([TF1] conv2d_transpose 'same': out o receives in i through kernel
+// index p with o = i*S + p - S/2, k = 2S): sources i1 = (o + S/2) / S with p1 = (o + S/2) % S and
+// i0 = i1 - 1 with p0 = p1 + S; 1-D weight w1[p] = 1 - |p/S - (2S-1-S%2)/(2S)| (custom_layers.py:15-21).
+// Out-of-range sources fall on the zero border of the padded layout and contribute exactly 0.
+template <int S>
+__device__ static inline void bilinear_taps(int o, int& i1, float& w_i1, float& w_i0) {
+#pragma clang fp contract(on)
+  const int t = o + S / 2;
+  i1 = t / S;
+  const int p1 = t - i1 * S;
+  constexpr float center = (2.f * S - 1.f - (S % 2)) / (2.f * S);
+  w_i1 = 1.f - fabsf((float)p1 / S - center);
+  w_i0 = 1.f - fabsf((float)(p1 + S) / S - center);
+}
+
+// ---- exact three-way bf16 split of fp32 MFMA operands (conv_first.hip, conv_first_fused.hip, batchnorm.hip) ------------------
+// The k-slot map of conv1_1 on 16 x 16 x 32 bf16 MFMAs (K = 9 CIN <= 27 fits one MFMA): k-group g (8 values, lanes 16 g ..
+// 16 g + 15) holds image row dy = g, columns dx = 0..2 x CIN channels in memory order (8 of its 9 values for CIN = 3); the
+// three leftover values (dx = 2, ci = 2 of each row) form k-group 3, whose first spare slot carries the bias.
+template <int CIN>
+__device__ static __forceinline__ bool first_k_map(int g, int e, int& dy, int& dx, int& ci) {
+  if (CIN == 3) {
+    if (g < 3) {
+      dy = g, dx = e / 3, ci = e % 3;
+      return true;
+    }
+    dy = e, dx = 2, ci = 2;
+    return e < 3;
+  }
+  dy = g, dx = e, ci = 0;  // CIN == 1
+  return g < 3 && e < 3;
+}
+
+// v = h + m + l exactly, each term a bf16 (returned as fp32 bit patterns with zero low halves): truncation keeps the
+// top 8 significant bits, the remainder of a 24-bit significand has at most 16, then at most 8
+__device__ static __forceinline__ void split3_bf16(float v, uint32_t& h, uint32_t& m, uint32_t& l) {
+  h = __builtin_bit_cast(uint32_t, v) & 0xffff0000u;
+  const float r1 = v - __builtin_bit_cast(float, h);  // exact
+  m = __builtin_bit_cast(uint32_t, r1) & 0xffff0000u;
+  l = __builtin_bit_cast(uint32_t, r1 - __builtin_bit_cast(float, m));  // exact, fits 8 bits
+}
+__device__ static __forceinline__ uint32_t hi16_pair(uint32_t a, uint32_t b) {  // (a >> 16) | (b & 0xffff0000): v_perm_b32
+  return __builtin_amdgcn_perm(b, a, 0x07060302u);
+}
+__device__ static __forceinline__ void split3_bf16x8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
+  uint32_t hh[8], mm[8], ll[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) split3_bf16(v[e], hh[e], mm[e], ll[e]);
+  h = __builtin_bit_cast(bf16x8, u32x4{hi16_pair(hh[0], hh[1]), hi16_pair(hh[2], hh[3]), hi16_pair(hh[4], hh[5]), hi16_pair(hh[6], hh[7])});
+  m = __builtin_bit_cast(bf16x8, u32x4{hi16_pair(mm[0], mm[1]), hi16_pair(mm[2], mm[3]), hi16_pair(mm[4], mm[5]), hi16_pair(mm[6], mm[7])});
+  l = __builtin_bit_cast(bf16x8, u32x4{hi16_pair(ll[0], ll[1]), hi16_pair(ll[2], ll[3]), hi16_pair(ll[4], ll[5]), hi16_pair(ll[6], ll[7])});
+}
+
 // Output-side helpers shared by the MFMA conv kernels (a lane holds 4 consecutive output channels of one pixel for
 // each of the four 16-channel blocks).
 __device__ static __forceinline__ void xv_pair16(const u32x2 a, const u32x2 b, u32x4& out) {
@@ -168,7 +245,7 @@ __device__ static __forceinline__ float xv_fast_log(float x) { return __builtin_
 __device__ static __forceinline__ float xv_fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 // Certainty-weighted fusion of the MC-dropout model (variance_mix.py:7-15): fused[k] = sum_e p_e[k] c_e / sum_e c_e with the
-// certainty c_e = 1 / (1e-20 + var_e).  The variance head (pointwise.hip) and xv_variance_fuse (fusion.hip) both run these two
+// certainty c_e = 1 / (1e-20 + var_e).  The variance head (heads.hip) and xv_variance_fuse (fusion.hip) both run these two
 // functions, experts in the same order, so their labels agree bit for bit.  Contraction is off inside them: a caller's
 // product must not be fused into `1e-20 + var` in one kernel and not in the other.
 template <int CM>
@@ -210,7 +287,7 @@ __device__ static __forceinline__ int xv_variance_fuse_finish(float (&acc)[CM], 
 // summed and scaled, need not be that value); a negative rounding residue of m2 is clamped per class, so variance >= 0.
 // T = 1: mean = p_1, so entropy and cond_entropy are the same expression on the same bits.  Two rows of state (mean, m2) where
 // the shifted sums of variance_head_kernel take three: at 16 classes that is what keeps the head at four waves per SIMD.
-// The head (pointwise.hip, mc_uncertainty_head_kernel) and xv_sampling_uncertainty (fusion.hip) both run these functions, so
+// The head (heads.hip, mc_uncertainty_head_kernel) and xv_sampling_uncertainty (fusion.hip) both run these functions, so
 // equal p_t give equal bits; contraction is off inside them so that neither caller's context decides where an fma forms.
 // Lanes k >= C are ignored.
 template <int CM>
@@ -276,7 +353,7 @@ __device__ static __forceinline__ int xv_mc_finish(const float (&mean)[CM], cons
 // statically indexed registers).  `A` is one expert's table in LDS, TRANSPOSED and padded with zeros: A[c * CM + j] = A[j][c];
 // `cs[c]` = sum_j A[j][c] rounded once from double: sum_j alpha[j][c] = cs[c] (1 - mix) + mix (C + 1) is linear in mix.
 // mix = 1 gives alpha = 1 + delta_jc exactly, whatever A holds; mix = 0 gives alpha = A exactly.  Renormalisation and logarithm
-// are those of dirichlet_fuse_kernel (xv_fast_rcp, xv_fast_log).  The fusion head (pointwise.hip) and
+// are those of dirichlet_fuse_kernel (xv_fast_rcp, xv_fast_log).  The fusion head (heads.hip) and
 // xv_uncertainty_dirichlet_fuse (fusion.hip) both run these functions: equal p, mvar and vmax give equal bits, for any CM >= C
 // (padding adds exact zeros); contraction is off inside them.  max variance 0 (identical samples everywhere; the reference
 // divides 0 / 0 there) gives mix = 0, the plain Dirichlet fusion.

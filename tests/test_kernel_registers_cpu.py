@@ -13,9 +13,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 BUDGETS = [
     ('backward.hip', 'head_loss_kernelILi12ELb1E', 2, 0),                  # 253 registers; 412 before the taps were loaded once
     ('backward.hip', 'count_valid_kernel', 4, 0),
-    ('pointwise.hip', 'fused_dirichlet_head_pk_kernelILi12ELi4E', 3, 0),   # 162 registers
-    ('pointwise.hip', 'fused_head_kernelILi12ELi0ELb1ELi4E', 4, 0),        # Bayes: 98 registers (168 with per-pixel class sums)
-    ('pointwise.hip', 'decoder_head_label4_kernelILi12E', 5, 0),
+    ('heads.hip', 'fused_dirichlet_head_pk_kernelILi12ELi4E', 3, 0),       # 162 registers
+    ('heads.hip', 'fused_head_kernelILi12ELi0ELb1ELi4E', 4, 0),            # Bayes: 98 registers (168 with per-pixel class sums)
+    ('heads.hip', 'decoder_head_label4_kernelILi12E', 5, 0),
     ('fusion.hip', 'dirichlet_fuse_pk_kernelILi12E', 6, 0),                # 66 registers; 372 inside a grid-stride loop
     # round 6: the fused first pair carried 32 bytes of scratch in its RGB forms -- the masked tap gather of its edge-tile path
     # selected between array elements, which the compiler turned into an indexed load from a stack copy of the array

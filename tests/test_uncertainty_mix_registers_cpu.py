@@ -16,10 +16,10 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 # (file, mangled-name fragment, fewest waves per SIMD, most scratch bytes)
 BUDGETS = [
-    ('pointwise.hip', 'uncertainty_dirichlet_head_kernelILi12E', 5, 0),     # 83 registers
-    ('pointwise.hip', 'uncertainty_dirichlet_head_kernelILi', 1, 0),        # every instantiation: no scratch
-    ('pointwise.hip', 'uncertainty_moments_kernelILi12E', 4, 0),            # 84 registers (five waves)
-    ('pointwise.hip', 'uncertainty_moments_kernelILi', 1, 0),
+    ('heads.hip', 'uncertainty_dirichlet_head_kernelILi12E', 5, 0),         # 83 registers
+    ('heads.hip', 'uncertainty_dirichlet_head_kernelILi', 1, 0),            # every instantiation: no scratch
+    ('heads.hip', 'uncertainty_moments_kernelILi12E', 4, 0),                # 84 registers (five waves)
+    ('heads.hip', 'uncertainty_moments_kernelILi', 1, 0),
     ('pointwise.hip', 'pixel_dropout_kernel', 4, 0),                        # 11 registers
     ('fusion.hip', 'uncertainty_dirichlet_fuse_kernelILi12E', 5, 0),        # 84 registers
     ('fusion.hip', 'uncertainty_dirichlet_fuse_kernelILi', 1, 0),

@@ -14,9 +14,9 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 # (file, mangled-name fragment, fewest waves per SIMD, most scratch bytes)
 BUDGETS = [
-    ('pointwise.hip', 'mc_uncertainty_head_kernelILi12E', 4, 0),
-    ('pointwise.hip', 'mc_uncertainty_head_kernelILi16E', 4, 0),
-    ('pointwise.hip', 'mc_uncertainty_head_kernelILi', 1, 0),        # every instantiation the variance head has: no scratch
+    ('heads.hip', 'mc_uncertainty_head_kernelILi12E', 4, 0),
+    ('heads.hip', 'mc_uncertainty_head_kernelILi16E', 4, 0),
+    ('heads.hip', 'mc_uncertainty_head_kernelILi', 1, 0),            # every instantiation the variance head has: no scratch
     ('pointwise.hip', 'dropout_samples_kernel', 4, 0),
     ('fusion.hip', 'sampling_uncertainty_kernelILi16E', 4, 0),
     ('fusion.hip', 'sampling_uncertainty_kernelILi32E', 1, 0),
@@ -43,7 +43,7 @@ def test_register_budgets_of_the_uncertainty_kernels():
             assert waves >= min_waves and scratch <= max_scratch, \
                 '%s: %d waves per SIMD (%d registers), %d B scratch; budget: >= %d waves, <= %d B' % (
                     kern, waves, regs, scratch, min_waves, max_scratch)
-    heads = {r[0] for r in table['pointwise.hip'] if 'mc_uncertainty_head_kernelILi' in r[0]}
+    heads = {r[0] for r in table['heads.hip'] if 'mc_uncertainty_head_kernelILi' in r[0]}
     assert len(heads) == 8, sorted(heads)                            # CM = 4, 8, .. 32, as variance_head_kernel
 
 

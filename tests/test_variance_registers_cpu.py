@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 
 # (file, mangled-name fragment, fewest waves per SIMD, most scratch bytes)
 BUDGETS = [
-    ('pointwise.hip', 'variance_head_kernelILi12E', 4, 0),
+    ('heads.hip', 'variance_head_kernelILi12E', 4, 0),
     ('pointwise.hip', 'dropout_samples_kernel', 4, 0),
     ('fusion.hip', 'variance_fuse_kernelILi16E', 4, 0),
 ]

@@ -5,6 +5,7 @@ compiler keeps loop-invariant LDS tables in registers and requests every indepen
 head_loss_kernel at 412 registers, a Dirichlet kernel at 372): a scan of this table after a kernel change finds that in a
 minute.  tests/test_kernel_registers_cpu.py pins the budgets of the kernels that were caught."""
 import concurrent.futures
+import hashlib
 import os
 import re
 import shutil
@@ -15,11 +16,14 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'modular_semantic_segmentation_amd', 'csrc')
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-S', '--cuda-device-only']
-EXTRA = {'pointwise.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}      # as the Makefile builds it
+EXTRA = {'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}     # as the Makefile builds it
 
 
-def scan_file(path):
-    """[(mangled kernel name, total VGPRs incl. AGPRs, scratch bytes, waves per SIMD)] of one source file."""
+def scan_file(path, digest=False):
+    """[(mangled kernel name, total VGPRs incl. AGPRs, scratch bytes, waves per SIMD)] of one source file; with `digest` a fifth
+    column: sha256 of the kernel's assembly text from its label to .Lfunc_end, the kernel's ordinal within the file taken out
+    of the local labels (.LBB<n>_<m>, .LJTI<n>_<m>) and runs of blanks made one (a label's length sets the column of the comment
+    behind it), so that a kernel that moves to another file keeps its digest."""
     name = os.path.basename(path)
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, name + '.s')
@@ -27,17 +31,21 @@ def scan_file(path):
                            cwd=os.path.dirname(path))
         if r.returncode != 0:
             raise RuntimeError('hipcc -S %s failed:\n%s' % (name, r.stderr[-2000:]))
-        rows, kern, tot, scr = [], None, None, None
+        rows, kern, tot, scr, body = [], None, None, None, None
         for line in open(out):
             m = re.match(r'^(_Z\S+):', line)
             if m:
-                kern = m.group(1)
+                kern, body = m.group(1), hashlib.sha256()
+            elif line.startswith('.Lfunc_end'):
+                sha, body = body.hexdigest()[:16], None
+            elif body is not None:
+                body.update(re.sub(r'\s+', ' ', re.sub(r'\b(L?BB|LJTI)\d+_', r'\1_', line)).encode())
             elif line.startswith('; TotalNumVgprs:'):
                 tot = int(line.split(':')[1])
             elif line.startswith('; ScratchSize:'):
                 scr = int(line.split(':')[1])
             elif line.startswith('; Occupancy:'):
-                rows.append((kern, tot, scr, int(line.split(':')[1])))
+                rows.append((kern, tot, scr, int(line.split(':')[1])) + ((sha,) if digest else ()))
         return rows
 
 
@@ -59,9 +67,17 @@ if __name__ == '__main__':
     if any(a in ('-h', '--help') for a in sys.argv[1:]):
         print(__doc__)
         print('  --all   list every kernel, not only the flagged ones')
+        print('  --digest   one line per kernel, "<sha256 of its assembly text> <mangled name>", sorted by name: diff two of these')
+        print('             listings to show that a change left every kernel\'s machine code as it was')
         sys.exit(0)
     show_all = '--all' in sys.argv[1:]
     args = [os.path.abspath(a) for a in sys.argv[1:] if not a.startswith('--')]
+    if '--digest' in sys.argv[1:]:
+        files = args or sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
+        with concurrent.futures.ThreadPoolExecutor(16) as ex:
+            rows = [r for rows in ex.map(lambda f: scan_file(f, digest=True), files) for r in rows]
+        print('\n'.join('%s %s' % (r[4], r[0]) for r in sorted(rows)))
+        sys.exit(0)
     for fname, rows in scan(args or None).items():
         flagged = [r for r in rows if show_all or r[3] <= 2 or r[2] > 0]
         print('%s: %d kernels, %d at <= 2 waves per SIMD or with scratch' % (fname, len(rows), len(flagged)))
