@@ -502,6 +502,19 @@ int xv_mc_uncertainty_head_fwd(const float* S, const float* bias, int n, int hi,
                                int64_t* label, float* mean_prob, float* entropy, float* cond_entropy, float* variance,
                                void* stream);
 
+/* Scoring form of the uncertainty head (uncertainty_model.py; experiments/uncertainty_eval.py:18-52,62-88): S, bias, n, hi, wi,
+ * num_classes, num_samples as xv_mc_uncertainty_head_fwd takes them; every interpolated logit is multiplied by inv_temperature
+ * before the softmax (custom_layers.py:239-248; 1.0f gives the bits of that head).  The pixel's entropy, cond_entropy and
+ * variance are binned as xv_uncertainty_stats bins a metric, into hist uint64 [3][2][octaves << mantissa_bits] in that order,
+ * row = (argmax of the mean != label) over the pixels with 0 <= label < C (fixed_row = -1), or row fixed_row (0 or 1) for
+ * every pixel; labels int32 [n][8hi][8wi] (may be null with a fixed row) also feed nll double [C], nll[label] -=
+ * ln(clip(mean[label], 1e-10, 1)), and counts int64 [C] over the valid pixels.  All three are accumulated, not cleared; no
+ * per-pixel map is written.  XV_EINVAL for num_classes < 2, mantissa_bits outside 3..8, octaves outside 8..32, or tables that
+ * do not fit a workgroup's LDS (more than 64 KB for one copy). */
+int xv_mc_uncertainty_score_fwd(const float* S, const float* bias, int n, int hi, int wi, int num_classes, int num_samples,
+                                float inv_temperature, const int32_t* labels, int mantissa_bits, int octaves, int fixed_row,
+                                uint64_t* hist, double* nll, int64_t* counts, void* stream);
+
 /* ---- uncertainty-weighted Dirichlet fusion (uncertainty_dirichlet_mix.py) ---------------------------------------------
  * Dropout of the network input, whole pixels at a time (noise_shape [N,H,W,1]): x dense float [n][h][w][cin]; y holds
  * plain + num_samples slots of it, slot-major: slot 0 a copy of x when plain == 1, sample t = 0 .. num_samples-1 with ONE
@@ -574,6 +587,17 @@ int xv_dirichlet_suffstats(const float* prob, const int32_t* labels, int num_cla
  * labels are the dropped (C+1)-th row); cm int64 [C][C], accumulated, rows = ground truth.         */
 int xv_confusion_matrix(const int32_t* labels, const int64_t* pred, int num_classes, int64_t npix,
                         int64_t* cm, void* stream);
+/* Uncertainty benchmarks on materialised maps (uncertainty_model.py): metric float [npix] (one uncertainty map), pred int64
+ * [npix], labels int32 [npix].  hist uint64 [2][bins], bins = octaves << mantissa_bits: hist[row][bin(metric)] += 1 with
+ * row = (pred != label) over the pixels with 0 <= label < C (fixed_row = -1), or row fixed_row (0 or 1) for EVERY pixel (pred
+ * and labels may then be null).  bin(v) comes from the float's bits: v <= 0 -> 0, NaN -> bins - 1, else
+ * (bits(v) >> (23 - mantissa_bits)) - ((128 - octaves) << mantissa_bits) clamped to [0, bins - 1].  mean_prob float [npix][C]
+ * (optional; needs labels): nll double [C], nll[label] -= ln(clip(mean_prob[label], 1e-10, 1)), counts int64 [C] += 1, over
+ * the valid pixels; null leaves nll / counts untouched.  Everything is accumulated, not cleared.  XV_EINVAL for C < 2,
+ * mantissa_bits outside 3..8, octaves outside 8..32, or tables beyond 64 KB of LDS. */
+int xv_uncertainty_stats(const float* metric, const int64_t* pred, const int32_t* labels, const float* mean_prob,
+                         int num_classes, int64_t npix, int mantissa_bits, int octaves, int fixed_row, uint64_t* hist,
+                         double* nll, int64_t* counts, void* stream);
 /* Label maps on their way to the host (predict(), base_model.py:279-288): int64 labels in [0, 256) -> one byte per pixel,
  * out[i] = (uint8) labels[i].  The pipelined host boundary sends this image over PCIe (an eighth of the bytes) and widens it
  * to the reference's np.int64 while it fills the result array.  labels 16-byte, out 8-byte aligned.                       */

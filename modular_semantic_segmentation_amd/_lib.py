@@ -113,6 +113,7 @@ SIGNATURES = {
     'xv_fused_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'xv_variance_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'xv_mc_uncertainty_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xv_mc_uncertainty_score_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'xv_dropout_pixels_samples': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'xv_uncertainty_moments': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'xv_uncertainty_dirichlet_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -185,6 +186,7 @@ SIGNATURES = {
     'xv_adagrad_step': (_i, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, _vp]),
     'xv_dirichlet_suffstats': (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     'xv_confusion_matrix': (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    'xv_uncertainty_stats': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'xv_narrow_labels': (_i, [_vp, _i64, _vp, _vp]),
 }
 

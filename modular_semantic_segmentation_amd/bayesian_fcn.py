@@ -18,6 +18,7 @@ import torch
 from . import ops
 from .base_model import iterate_batches
 from .simple_fcn import SimpleFCN
+from .uncertainty_model import UncertaintyModel
 
 OUTPUTS = ('label', 'mean', 'entropy', 'cond_entropy', 'variance')
 
@@ -42,7 +43,7 @@ def sampling_uncertainty(inputs, pipeline, num_samples, num_classes, **kwargs):
     return out['mean'], {k: out[k] for k in ('entropy', 'cond_entropy', 'variance')}
 
 
-class BayesianFCN(SimpleFCN):
+class BayesianFCN(UncertaintyModel, SimpleFCN):
     """Args as the reference: prefix, data_description, modality, output_dir, dropout_layers (default: every site), **config
     with required `num_units`, `dropout_rate`, `num_samples`; optional `method` ('sampling', the only one), `dropout_seed`
     (default: `seed`, else 0), `mc_chunk_images` (default 64: most images one launch of the sampled layers sees).  Variables,
@@ -52,6 +53,13 @@ class BayesianFCN(SimpleFCN):
     'variance' ([N,H,W]) return one map; predict_uncertainty(data) returns all of them from ONE set of masks.  Every call
     draws new masks (the engine's pass counter advances by num_samples), so the step is never captured into a hipGraph: a
     replay would redraw the masks of the captured call.
+
+    The uncertainty benchmarks are UncertaintyModel's (uncertainty_model.py: misclassification_detection_score,
+    out_of_distribution_detection_score, nll_score, value_distribution, uncertainty_tables, temperature_search); a batch goes
+    through the scoring form of the head (ops.mc_uncertainty_score), which bins the three metrics and sums the NLL where the
+    head above stores its maps.  Optional `temperature_scaling` (default 1; custom_layers.py:239-248) divides the logits of
+    the benchmarks; predict() / predict_uncertainty() raise NotImplementedError under another value: the map-writing head has
+    no temperature, and the key is never ignored silently.
 
     Inference only: fit() raises NotImplementedError.  The reference trains this model WITH dropout (is_training=True: masks
     in the forward pass and their gradient in the backward pass), which the trainer does not do yet; train the same weights as
@@ -92,10 +100,32 @@ class BayesianFCN(SimpleFCN):
     def _train_batch(self, batch):
         self.fit()
 
-    def _uncertainty_of_batch(self, batch, want):
+    def _sample_scores(self, batch):
         x = self._to_device(batch[self.modality], torch.float32)
-        S, (n, hi, wi) = self.engine.mc_sample_scores(x, int(self.config['num_samples']), float(self.config['dropout_rate']),
-                                                      self._dropout_seed, self.config['dropout_layers'])
+        return self.engine.mc_sample_scores(x, int(self.config['num_samples']), float(self.config['dropout_rate']),
+                                            self._dropout_seed, self.config['dropout_layers'])
+
+    # ---- UncertaintyModel: the fused scoring head -------------------------------------------------------------------------------
+    def _uncertainty_maps(self, batch):
+        return self._uncertainty_of_batch(batch, OUTPUTS)
+
+    def _uncertainty_state(self, batch):
+        return self._sample_scores(batch)
+
+    def _uncertainty_accumulate(self, state, labels, tables, temperature, fixed_row):
+        S, (n, hi, wi) = state
+        m, o = self._uncertainty_bins()
+        ops.mc_uncertainty_score(S, self.engine.b['score'], n, hi, wi, self.config['num_classes'], int(self.config['num_samples']),
+                                 labels=labels, temperature=temperature, fixed_row=fixed_row, mantissa_bits=m, octaves=o,
+                                 tables=tables)
+
+    def _uncertainty_of_batch(self, batch, want):
+        if float(self.config.get('temperature_scaling', 1)) != 1.0:
+            raise NotImplementedError('BayesianFCN: temperature_scaling=%r applies to the uncertainty benchmarks only '
+                                      '(uncertainty_tables, temperature_search, ...); the head that writes label and maps has '
+                                      'no temperature, so predict() / predict_uncertainty() need temperature_scaling=1'
+                                      % (self.config['temperature_scaling'],))
+        S, (n, hi, wi) = self._sample_scores(batch)
         return ops.mc_uncertainty_head(S, self.engine.b['score'], n, hi, wi, self.config['num_classes'],
                                        int(self.config['num_samples']), want_mean='mean' in want,
                                        want_entropy='entropy' in want, want_cond_entropy='cond_entropy' in want,

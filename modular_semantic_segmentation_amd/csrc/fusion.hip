@@ -571,6 +571,59 @@ __global__ __launch_bounds__(1024) void confusion_kernel(const int32_t* __restri
   }
 }
 
+// uncertainty_model.py (experiments/uncertainty_eval.py:18-52): the benchmarks' statistic on MATERIALISED maps.  Per pixel ONE
+// metric value -> hist[row][xv_unc_bin(value)] += 1, row = (pred != label) over the pixels with 0 <= label < C, or the caller's
+// fixed row over every pixel; with `mean` ([npix][C]) also nll[label] -= ln(clip(mean[label], 1e-10, 1)), counts[label] += 1
+// over the valid pixels.  The replicated tables of suffstats_kernel / confusion_kernel (copy = lane & (rep - 1) fastest:
+// uncertainty maps are spatially smooth, so the lanes of a wave meet on ONE bin -- only lanes that share a copy serialise):
+// u32 histogram copies, double / u64 NLL copies, one global atomic per non-zero cell and workgroup.  Four pixels per thread
+// and step through 16-byte loads (metric quad, label quad, two prediction pairs) where the maps are 16-byte aligned; the NLL
+// reads the ONE probability it needs, a 4-byte gather at a 4 C-byte stride.
+__global__ __launch_bounds__(1024) void uncertainty_stats_kernel(const float* __restrict__ metric, const int64_t* __restrict__ pred,
+                                                               const int32_t* __restrict__ labels, const float* __restrict__ mean,
+                                                               int C, int64_t npix, int M, int octaves, int fixed_row,
+                                                               unsigned long long* __restrict__ hist, double* __restrict__ nll,
+                                                               unsigned long long* __restrict__ counts, int XV_REP, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double unc_nll[];  // nll [ncls][XV_REP], cnt [ncls][XV_REP], hist [2][bins][XV_REP]
+  const int ncls = mean ? C : 0, bins = octaves << M;
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(unc_nll + ncls * XV_REP);
+  uint32_t* hs = reinterpret_cast<uint32_t*>(unc_nll + 2 * ncls * XV_REP);
+  xv_unc_tables_zero(unc_nll, ncls, hs, 2 * bins, XV_REP);
+  __syncthreads();
+  const int T = blockDim.x;
+  const int rep = threadIdx.x & (XV_REP - 1);
+  auto count = [&](int64_t pix, float v, int l, int64_t p) {
+    const bool valid = l >= 0 && l < C;
+    if (fixed_row >= 0 || valid) {
+      const int row = fixed_row >= 0 ? fixed_row : (p != (int64_t)l);
+      atomicAdd(&hs[(row * bins + xv_unc_bin(v, M, octaves)) * XV_REP + rep], 1u);
+    }
+    if (ncls && valid) {
+      atomicAdd(&unc_nll[l * XV_REP + rep], xv_unc_nll_term(mean[pix * C + l]));
+      atomicAdd(&cnt[l * XV_REP + rep], 1ull);
+    }
+  };
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  typedef long long i64x2 __attribute__((ext_vector_type(2)));
+  const int64_t quads = vec ? npix >> 2 : 0, stride = (int64_t)gridDim.x * T;
+  for (int64_t q = (int64_t)blockIdx.x * T + threadIdx.x; q < quads; q += stride) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(metric + 4 * q);
+    i32x4 l = {-1, -1, -1, -1};
+    i64x2 p0 = {0, 0}, p1 = {0, 0};
+    if (labels) l = *reinterpret_cast<const i32x4*>(labels + 4 * q);
+    if (pred) p0 = *reinterpret_cast<const i64x2*>(pred + 4 * q), p1 = *reinterpret_cast<const i64x2*>(pred + 4 * q + 2);
+    count(4 * q, v.x, l.x, p0.x);
+    count(4 * q + 1, v.y, l.y, p0.y);
+    count(4 * q + 2, v.z, l.z, p1.x);
+    count(4 * q + 3, v.w, l.w, p1.y);
+  }
+  // the tail of the vector form / the whole map where a pointer is not 16-byte aligned
+  for (int64_t pix = 4 * quads + (int64_t)blockIdx.x * T + threadIdx.x; pix < npix; pix += stride)
+    count(pix, metric[pix], labels ? labels[pix] : -1, pred ? pred[pix] : 0);
+  __syncthreads();
+  xv_unc_tables_flush(unc_nll, ncls, hs, 2 * bins, XV_REP, hist, nll, counts);
+}
+
 // int64 label map -> one byte per pixel for the trip to the host (predict()'s return value is np.int64 [N,H,W],
 // base_model.py:279-288: the host widens it again while it fills the result array).  8 labels per thread: four 16-byte
 // reads, one 8-byte store.
@@ -793,5 +846,25 @@ extern "C" int xv_confusion_matrix(const int32_t* labels, const int64_t* pred, i
   // one 16-wave workgroup per CU: each ends with C*C same-address atomics, which serialise across the chip (~12 ns each)
   hipLaunchKernelGGL(confusion_kernel, dim3(xv_grid_for((npix + 7) / 8, 1024, xv_num_cus())), dim3(1024), lds,
                      (hipStream_t)stream, labels, pred, num_classes, npix, reinterpret_cast<unsigned long long*>(cm), rep, vec);
+  return xv_launch_status();
+}
+
+extern "C" int xv_uncertainty_stats(const float* metric, const int64_t* pred, const int32_t* labels, const float* mean_prob,
+                                    int num_classes, int64_t npix, int mantissa_bits, int octaves, int fixed_row, uint64_t* hist,
+                                    double* nll, int64_t* counts, void* stream) {
+  XV_CHECK_ARG(metric && hist && num_classes >= 2 && mantissa_bits >= 3 && mantissa_bits <= 8 && octaves >= 8 && octaves <= 32);
+  XV_CHECK_ARG(fixed_row >= -1 && fixed_row <= 1 && (fixed_row >= 0 || (pred && labels)));
+  XV_CHECK_ARG(!mean_prob || (labels && nll && counts));
+  XV_CHECK_SHAPE(num_classes <= 64 && npix > 0 && npix <= ((int64_t)1 << 36));
+  // one copy: the two histogram rows and, with mean_prob, the NLL sums and counts; as many copies as fit the 64 KB of
+  // suffstats_kernel / confusion_kernel
+  const size_t per_copy = (size_t)(octaves << mantissa_bits) * 2 * 4 + (mean_prob ? (size_t)num_classes * 16 : 0);
+  const int rep = table_copies(per_copy, 1);
+  XV_CHECK_ARG(per_copy * rep <= 64 * 1024);
+  const int vec = (((uintptr_t)metric | (uintptr_t)pred | (uintptr_t)labels) & 15) == 0;
+  // one 16-wave workgroup per CU, as confusion_kernel
+  hipLaunchKernelGGL(uncertainty_stats_kernel, dim3(xv_grid_for((npix + 3) / 4, 1024, xv_num_cus())), dim3(1024), per_copy * rep,
+                     (hipStream_t)stream, metric, pred, labels, mean_prob, num_classes, npix, mantissa_bits, octaves, fixed_row,
+                     reinterpret_cast<unsigned long long*>(hist), nll, reinterpret_cast<unsigned long long*>(counts), rep, vec);
   return xv_launch_status();
 }

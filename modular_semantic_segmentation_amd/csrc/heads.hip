@@ -553,6 +553,75 @@ __global__ __launch_bounds__(256) void mc_uncertainty_head_kernel(const float* _
   if (var_out) var_out[opix] = var;
 }
 
+// ---- scoring form of the uncertainty head (uncertainty_model.py; experiments/uncertainty_eval.py:18-52,62-88): the per-pixel
+// work of mc_uncertainty_head_kernel, statement for statement (head_logits / head_max / head_softmax per sample, then
+// xv_mc_first / xv_mc_add / xv_mc_finish with every output wanted), with custom_layers.py:239-248's temperature: every
+// interpolated logit times inv_temperature before the softmax (1.0f multiplies exactly: the bits of the head above; a power of
+// two scales exactly: temperature 2 on S, bias is temperature 1 on S / 2, bias / 2).  The pixel's three values, its label and
+// mean[label] go straight into the workgroup's replicated LDS tables (xv_common.h: nll / counts [C], hist [3][2][bins] in the
+// order entropy, cond_entropy, variance; copy = lane & (rep - 1) fastest) -- NO map reaches HBM.  row = (argmax != label)
+// over the pixels with 0 <= label < C, or the caller's fixed row over every pixel; NLL over the valid pixels either way.  A
+// bounded grid (four 256-thread workgroups per CU, the four waves per SIMD of the register budget), pixels in a grid-stride
+// loop, one global atomic per non-zero cell and workgroup.
+template <int CM>
+__device__ __forceinline__ void head_prob_scaled(const float* __restrict__ S, const float* __restrict__ bs_g, int n, int oy, int ox,
+                                                 int Hi, int Wi, int C, float inv_t, float (&sc)[CM]) {
+  head_logits<CM>(S, bs_g, n, oy, ox, Hi, Wi, C, sc);
+#pragma unroll
+  for (int k = 0; k < CM; ++k) sc[k] = sc[k] * inv_t;
+  const float m = head_max<CM>(sc, C);
+  head_softmax<CM>(sc, m, C);
+}
+
+template <int CM>
+__global__ __launch_bounds__(256) void mc_uncertainty_score_kernel(const float* __restrict__ S, const float* __restrict__ bs, int N,
+                                                                  int Hi, int Wi, int C, int T, float ln_c, float inv_t,
+                                                                  const int32_t* __restrict__ labels, int M, int octaves,
+                                                                  int fixed_row, unsigned long long* __restrict__ hist,
+                                                                  double* __restrict__ nll, unsigned long long* __restrict__ counts,
+                                                                  int XV_REP) {
+  extern __shared__ __attribute__((aligned(16))) double unc_nll[];  // nll [C][XV_REP], cnt [C][XV_REP], hist [3][2][bins][XV_REP]
+  const int ncls = labels ? C : 0, bins = octaves << M;
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(unc_nll + ncls * XV_REP);
+  uint32_t* hs = reinterpret_cast<uint32_t*>(unc_nll + 2 * ncls * XV_REP);
+  xv_unc_tables_zero(unc_nll, ncls, hs, 6 * bins, XV_REP);
+  __syncthreads();
+  const int rep = threadIdx.x & (XV_REP - 1);
+  const int Ho = Hi * 8, Wo = Wi * 8;
+  const int64_t npix = (int64_t)N * Ho * Wo;
+  for (int64_t opix = (int64_t)blockIdx.x * 256 + threadIdx.x; opix < npix; opix += (int64_t)gridDim.x * 256) {
+    const int ox = (int)(opix % Wo);
+    const int oy = (int)((opix / Wo) % Ho);
+    const int n = (int)(opix / ((int64_t)Wo * Ho));
+    float mean[CM], m2[CM], sc[CM], ce;
+    head_prob_scaled<CM>(S, bs, n, oy, ox, Hi, Wi, C, inv_t, sc);
+    xv_mc_first<CM>(mean, m2, ce, sc, C, true);
+    for (int t = 1; t < T; ++t) {
+      head_prob_scaled<CM>(S, bs, t * N + n, oy, ox, Hi, Wi, C, inv_t, sc);
+      xv_mc_add<CM>(mean, m2, ce, sc, t + 1, C, true, true);
+    }
+    float ent, cond, var;
+    const int bi = xv_mc_finish<CM>(mean, m2, ce, T, C, ln_c, true, ent, cond, var);
+    const int l = labels ? labels[opix] : -1;
+    const bool valid = l >= 0 && l < C;
+    if (fixed_row >= 0 || valid) {
+      const int row = fixed_row >= 0 ? fixed_row : (bi != l);
+      atomicAdd(&hs[(row * bins + xv_unc_bin(ent, M, octaves)) * XV_REP + rep], 1u);
+      atomicAdd(&hs[((2 + row) * bins + xv_unc_bin(cond, M, octaves)) * XV_REP + rep], 1u);
+      atomicAdd(&hs[((4 + row) * bins + xv_unc_bin(var, M, octaves)) * XV_REP + rep], 1u);
+    }
+    if (valid) {
+      float pl = mean[0];  // mean[l] by selects: statically indexed registers
+#pragma unroll
+      for (int k = 1; k < CM; ++k) pl = k == l ? mean[k] : pl;
+      atomicAdd(&unc_nll[l * XV_REP + rep], xv_unc_nll_term(pl));
+      atomicAdd(&cnt[l * XV_REP + rep], 1ull);
+    }
+  }
+  __syncthreads();
+  xv_unc_tables_flush(unc_nll, ncls, hs, 6 * bins, XV_REP, hist, nll, counts);
+}
+
 // ---- uncertainty-weighted Dirichlet fusion (uncertainty_dirichlet_mix.py:18-52,221-233): moments pass and fusion head ------
 // Moments: both experts' low-resolution class scores of T + 1 passes (slot 0 plain, slots 1 .. T input-dropout samples; the
 // contract of variance_head_kernel) -> per expert mvar [2][N][8Hi][8Wi], the population variance of every class's probability
@@ -1116,6 +1185,35 @@ extern "C" int xv_mc_uncertainty_head_fwd(const float* S, const float* bias, int
                      ln_c, label, mean_prob, entropy, cond_entropy, variance)
   XV_CM_SWITCH(num_classes, XV_UH)
 #undef XV_UH
+  return xv_launch_status();
+}
+
+// Scoring form of the uncertainty head (see mc_uncertainty_score_kernel): S as xv_mc_uncertainty_head_fwd takes it.
+extern "C" int xv_mc_uncertainty_score_fwd(const float* S, const float* bias, int n, int hi, int wi, int num_classes,
+                                           int num_samples, float inv_temperature, const int32_t* labels, int mantissa_bits,
+                                           int octaves, int fixed_row, uint64_t* hist, double* nll, int64_t* counts,
+                                           void* stream) {
+  XV_CHECK_ARG(S && bias && hist && num_samples >= 1 && num_classes >= 2 && inv_temperature > 0.f);
+  XV_CHECK_ARG(mantissa_bits >= 3 && mantissa_bits <= 8 && octaves >= 8 && octaves <= 32);
+  XV_CHECK_ARG(fixed_row >= -1 && fixed_row <= 1 && (fixed_row >= 0 || labels) && (!labels || (nll && counts)));
+  XV_CHECK_SHAPE(num_classes <= 32 && num_samples <= 1024);
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi) && (int64_t)n * num_samples < ((int64_t)1 << 31));
+  const int64_t npix = (int64_t)n * hi * wi * 64;
+  // one copy: three histograms of two rows and, with labels, the NLL sums and counts.  Copies while four workgroups fit a
+  // CU's 160 KB of LDS (40 KB each); a single copy may take the 64 KB of the statistics kernels (two workgroups per CU).
+  const size_t per_copy = (size_t)(octaves << mantissa_bits) * 6 * 4 + (labels ? (size_t)num_classes * 16 : 0);
+  int rep = 8;
+  while (rep > 1 && per_copy * rep > 40 * 1024) rep >>= 1;
+  XV_CHECK_ARG(per_copy * rep <= 64 * 1024);
+  const unsigned grid = (unsigned)xv_grid_for(npix, 256, xv_num_cus() * 4);
+  const float ln_c = xv_ln_classes(num_classes);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_US(CMV)                                                                                                          \
+  hipLaunchKernelGGL(mc_uncertainty_score_kernel<CMV>, dim3(grid), dim3(256), per_copy * rep, s, S, bias, n, hi, wi, num_classes, \
+                     num_samples, ln_c, inv_temperature, labels, mantissa_bits, octaves, fixed_row,                         \
+                     reinterpret_cast<unsigned long long*>(hist), nll, reinterpret_cast<unsigned long long*>(counts), rep)
+  XV_CM_SWITCH(num_classes, XV_US)
+#undef XV_US
   return xv_launch_status();
 }
 

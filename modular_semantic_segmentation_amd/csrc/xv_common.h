@@ -445,6 +445,54 @@ __device__ static __forceinline__ void xv_block_max_nonneg(float v, uint32_t* re
   }
 }
 
+// ---- uncertainty benchmarks (uncertainty_model.py; xv_uncertainty_stats in fusion.hip, xv_mc_uncertainty_score_fwd in
+// heads.hip) -------------------------------------------------------------------------------------------------------------
+// Histogram bin of a metric value from its BIT PATTERN (non-negative floats order like their bits, as xv_block_max_nonneg
+// uses): M mantissa bits and `octaves` binades below 2 give octaves << M log-spaced bins of 2^-M relative width;
+// key = (bits >> (23 - M)) - ((128 - octaves) << M) clamped to [0, bins - 1].  v <= 0 (and -0.0) -> bin 0, NaN -> the top bin
+// (as every value >= 2 and +inf).  An exact function of the bits: uncertainty_model.bin_index is the same expression in numpy.
+__device__ static __forceinline__ int xv_unc_bin(float v, int M, int octaves) {
+  const int top = (octaves << M) - 1;
+  if (v != v) return top;
+  if (!(v > 0.f)) return 0;
+  const int key = (int)(__builtin_bit_cast(uint32_t, v) >> (23 - M)) - ((128 - octaves) << M);
+  return key < 0 ? 0 : (key > top ? top : key);
+}
+
+// One pixel's NLL term of the benchmarks, -ln(clip(p, 1e-10, 1)) with xv_fast_log after the clip (the logarithm of
+// xv_entropy_sum), as a double for the double sums.
+__device__ static __forceinline__ double xv_unc_nll_term(float p) {
+  return -(double)xv_fast_log(fminf(fmaxf(p, 1e-10f), 1.f));
+}
+
+// The replicated LDS tables of both kernels, index = cell * rep + copy: nll double [C][rep], cnt u64 [C][rep], then hist u32
+// [nhist][2][bins][rep].  Zeroed by the workgroup; at the end every cell's copies are summed and each non-zero cell costs ONE
+// global atomic.  `ncls` = 0: no NLL tables.
+__device__ static __forceinline__ void xv_unc_tables_zero(double* nll_s, int ncls, uint32_t* hist_s, int hcells, int rep) {
+  for (int i = threadIdx.x; i < 2 * ncls * rep; i += blockDim.x) nll_s[i] = 0.0;  // (0.0 and 0ull share their bits)
+  for (int i = threadIdx.x; i < hcells * rep; i += blockDim.x) hist_s[i] = 0u;
+}
+
+__device__ static __forceinline__ void xv_unc_tables_flush(const double* nll_s, int ncls, const uint32_t* hist_s, int hcells, int rep,
+                                                           unsigned long long* __restrict__ hist, double* __restrict__ nll,
+                                                           unsigned long long* __restrict__ counts) {
+  const unsigned long long* cnt_s = reinterpret_cast<const unsigned long long*>(nll_s + ncls * rep);
+  for (int i = threadIdx.x; i < hcells; i += blockDim.x) {
+    unsigned long long a = 0ull;
+    for (int r = 0; r < rep; ++r) a += hist_s[i * rep + r];
+    if (a) atomicAdd(&hist[i], a);
+  }
+  for (int i = threadIdx.x; i < ncls; i += blockDim.x) {
+    double s = 0.0;
+    unsigned long long a = 0ull;
+    for (int r = 0; r < rep; ++r) s += nll_s[i * rep + r], a += cnt_s[i * rep + r];
+    if (a) {
+      atomicAdd(&nll[i], s);
+      atomicAdd(&counts[i], a);
+    }
+  }
+}
+
 // Order-preserving map of packed bf16 bit patterns onto signed 16-bit integers (an involution: negative values have their
 // magnitude bits flipped), for a 2x2 max on packed pairs WITHOUT a preceding relu.
 __device__ static __forceinline__ uint32_t pk_ord_bf16(uint32_t x) {

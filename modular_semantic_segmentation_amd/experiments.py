@@ -1,6 +1,6 @@
 """The reference's evaluation / fusion experiment flows without the sacred experiment database
 (reference: experiments/evaluation.py:14-41,62-110, experiments/bayes_fusion.py:21-33,146-195,
-experiments/dirichlet_fusion.py:19-81, experiments/training.py).
+experiments/dirichlet_fusion.py:19-81, experiments/training.py, experiments/uncertainty_eval.py:18-52).
 
 Datasets here are dicts of arrays ({'rgb': [N,H,W,3], 'depth': [N,H,W,1], 'labels': [N,H,W]}) or any iterable of
 per-sample dicts (the data contract of base_model.iterate_batches); the reference's `tf.data` readers, the
@@ -101,3 +101,31 @@ def fit_and_evaluate_dirichlet_fusion(net_config, data_description, measure_set,
         import_weights_into_network(net, starting_weights)
         info['measurements'], info['confusion_matrix'] = net.score(test_set)
     return info
+
+
+def evaluate_uncertainty(net, data, metric, benchmark='misclassification', print_results=True, ood_data=None):
+    """experiments/uncertainty_eval.py:18-32: ROC and AUROC of one uncertainty metric of `net` (an UncertaintyModel) as a
+    detector of its misclassified pixels, or (benchmark 'out_of_distribution') of the pixels of `ood_data` among those of
+    `data` (the reference's base class drew the foreign set from the dataset itself; here it is an argument)."""
+    if benchmark == 'misclassification':
+        fpr, tpr, auroc, thresholds = net.misclassification_detection_score(data, metric)
+    elif benchmark == 'out_of_distribution':
+        if ood_data is None:
+            raise ValueError("benchmark 'out_of_distribution' needs ood_data")
+        fpr, tpr, auroc, thresholds = net.out_of_distribution_detection_score(data, metric, ood_data)
+    else:
+        raise ValueError('unknown benchmark %r' % (benchmark,))
+    if print_results:
+        print('Uncertainty Benchmark "{}" of {} on {} with {} metric'.format(benchmark, net.name, type(data).__name__, metric))
+        print('AUROC {:.3f}'.format(auroc))
+    return {'TPR': tpr, 'FPR': fpr, 'AUROC': auroc, 'thresholds': thresholds}
+
+
+def measure_metrics(net, data, metrics):
+    """experiments/uncertainty_eval.py:35-39 (its label_flip / mean_diff / prob_distribution parts belong to ambiguous-label
+    training, which is out of scope): {'nll', 'class_counts', and per metric its value_distribution}."""
+    nll, class_count = net.nll_score(data)
+    ret = {'nll': nll, 'class_counts': class_count}
+    for metric in metrics:
+        ret[metric] = net.value_distribution(data, metric)
+    return ret

@@ -642,6 +642,84 @@ def mc_uncertainty_head(S, bias, n, hi, wi, num_classes, num_samples, want_mean=
     return out
 
 
+UNCERTAINTY_METRICS = ('entropy', 'cond_entropy', 'variance')      # the order of mc_uncertainty_score's histograms
+
+
+def uncertainty_tables(num_classes, device, num_metrics=1, mantissa_bits=5, octaves=24):
+    """Zeroed accumulators of the uncertainty benchmarks: 'hist' (int64 [2, bins], or [num_metrics, 2, bins] for more than one
+    metric; bins = octaves << mantissa_bits), 'nll' (float64 [C]) and 'counts' (int64 [C])."""
+    bins = int(octaves) << int(mantissa_bits)
+    shape = (2, bins) if num_metrics == 1 else (num_metrics, 2, bins)
+    return {'hist': torch.zeros(shape, dtype=torch.int64, device=device),
+            'nll': torch.zeros(num_classes, dtype=torch.float64, device=device),
+            'counts': torch.zeros(num_classes, dtype=torch.int64, device=device)}
+
+
+def mc_uncertainty_score(S, bias, n, hi, wi, num_classes, num_samples, labels=None, temperature=1.0, fixed_row=-1,
+                         mantissa_bits=5, octaves=24, tables=None):
+    """The scoring form of mc_uncertainty_head (xv_mc_uncertainty_score_fwd): the same S and bias, logits divided by
+    `temperature`; accumulates into `tables` (uncertainty_tables(C, device, 3, ...), made here when None) the histograms of
+    entropy, cond_entropy and variance by row -- (label of the mean != labels) over the valid pixels, or `fixed_row` (0 / 1)
+    for every pixel -- and, with `labels` (int32 [n, 8hi, 8wi]), the NLL sums and class counts.  Returns the tables."""
+    _need(S, torch.float32, 'S')
+    _need(bias, torch.float32, 'bias')
+    T, C = int(num_samples), int(num_classes)
+    cp = (C + 3) // 4 * 4
+    if tuple(S.shape) != (T * n, hi + 2, wi + 2, cp):
+        raise ValueError('low-resolution scores of shape %s, expected %s' % (tuple(S.shape), (T * n, hi + 2, wi + 2, cp)))
+    if labels is not None:
+        _need(labels, torch.int32, 'labels')
+        if labels.numel() != n * hi * wi * 64:
+            raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+    if tables is None:
+        tables = uncertainty_tables(C, S.device, 3, mantissa_bits, octaves)
+    _check_uncertainty_tables(tables, C, (3, 2, int(octaves) << int(mantissa_bits)))
+    rc = _lib.lib().xv_mc_uncertainty_score_fwd(_ptr(S), _ptr(bias), n, hi, wi, C, T, 1.0 / float(temperature), _ptr(labels),
+                                               int(mantissa_bits), int(octaves), int(fixed_row), _ptr(tables['hist']),
+                                               _ptr(tables['nll']), _ptr(tables['counts']), _stream())
+    _lib.check(rc, 'xv_mc_uncertainty_score_fwd')
+    return tables
+
+
+def _check_uncertainty_tables(tables, num_classes, hist_shape):
+    _need(tables['hist'], torch.int64, 'hist')
+    _need(tables['nll'], torch.float64, 'nll')
+    _need(tables['counts'], torch.int64, 'counts')
+    if tuple(tables['hist'].shape) != tuple(hist_shape) or tables['nll'].numel() != num_classes or \
+            tables['counts'].numel() != num_classes:
+        raise ValueError('tables of shapes %s / %s / %s, expected %s and [%d]' % (
+            tuple(tables['hist'].shape), tuple(tables['nll'].shape), tuple(tables['counts'].shape), tuple(hist_shape),
+            num_classes))
+
+
+def uncertainty_stats(metric, pred, labels, num_classes, mean_prob=None, fixed_row=-1, mantissa_bits=5, octaves=24,
+                      tables=None):
+    """The benchmarks' statistic on materialised maps (xv_uncertainty_stats): metric float32 [...] (one uncertainty map), pred
+    int64 [...] and labels int32 [...] (both may be None with a fixed row).  Accumulates into `tables`
+    (uncertainty_tables(C, device), made here when None) hist[row][bin(metric)] with row = (pred != labels) over the valid
+    pixels or `fixed_row` for every pixel, and, with mean_prob (float32 [..., C]), the NLL sums and class counts.  Returns the
+    tables."""
+    _need(metric, torch.float32, 'metric')
+    if pred is not None:
+        _need(pred, torch.int64, 'pred')
+    if labels is not None:
+        _need(labels, torch.int32, 'labels')
+    if mean_prob is not None:
+        _need(mean_prob, torch.float32, 'mean_prob')
+    C, npix = int(num_classes), metric.numel()
+    for t, want in ((pred, npix), (labels, npix), (mean_prob, npix * C)):
+        if t is not None and t.numel() != want:
+            raise ValueError('maps of different sizes')
+    if tables is None:
+        tables = uncertainty_tables(C, metric.device, 1, mantissa_bits, octaves)
+    _check_uncertainty_tables(tables, C, (2, int(octaves) << int(mantissa_bits)))
+    rc = _lib.lib().xv_uncertainty_stats(_ptr(metric), _ptr(pred), _ptr(labels), _ptr(mean_prob), C, npix, int(mantissa_bits),
+                                        int(octaves), int(fixed_row), _ptr(tables['hist']), _ptr(tables['nll']),
+                                        _ptr(tables['counts']), _stream())
+    _lib.check(rc, 'xv_uncertainty_stats')
+    return tables
+
+
 def sampling_uncertainty(samples, want_label=True, want_mean=True, want_entropy=True, want_cond_entropy=True,
                          want_variance=True):
     """bayesian_fcn.py:48-57 on materialised samples float32 [T, ..., C] (xv_sampling_uncertainty) -> dict with the asked of
