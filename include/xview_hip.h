@@ -558,7 +558,10 @@ int xv_uncertainty_weights(const float* uncertainty, int num_classes, int64_t np
  * relu masks below `fused` are applied by the callers' next kernels).  valid_count must already hold the
  * batch's count.  workspace: xv_decoder_head_bwd_workspace_bytes(n, h, w, C) bytes, 16-byte aligned (the padded
  * 1/8-resolution scores, the row-weighted column sums of the score gradient -- the dense gradient is never stored --
- * and one slab of score-weight partial sums per 256 low-resolution pixels, reduced in a fixed order).   */
+ * and one slab of score-weight partial sums per 256 low-resolution pixels, reduced in a fixed order).
+ * Shapes: U = fused->c a multiple of 8, U <= 256, C <= 32, and with CM = C rounded up to 4 the slab kernel's LDS need
+ * (U CM + 256 CM) 4 + 512 U bytes must fit 160 KB (U = 256: C <= 16; C = 32: U <= 200; every U <= 128 fits every C).
+ * Anything else returns XV_ESHAPE before the first launch: loss, dw_score, db_score and dfused are untouched.   */
 size_t xv_decoder_head_bwd_workspace_bytes(int n, int h, int w, int num_classes);
 int xv_decoder_head_bwd(const xv_act* fused, const float* w_score, const float* b_score, const int32_t* labels,
                         const int64_t* valid_count, int num_classes, double* loss, float* dw_score,

@@ -803,6 +803,9 @@ extern "C" size_t xv_decoder_head_bwd_workspace_bytes(int n, int h, int w, int n
 
 extern "C" int xv_score_lowres(const xv_act* fused, const float* w_score, int num_classes, float* S, void* stream);
 
+// dynamic LDS of head_bwd_lowres_kernel<CM>: Ws [U][CM] and dS [256][CM] in fp32, fused [256][U] in bf16, of one 256-pixel slab
+static size_t head_bwd_lds_bytes(int U, int CM) { return ((size_t)U * CM + (size_t)256 * CM) * 4 + (size_t)256 * U * 2; }
+
 extern "C" int xv_decoder_head_bwd(const xv_act* fused, const float* w_score, const float* b_score, const int32_t* labels,
                                    const int64_t* valid_count, int num_classes, double* loss, float* dw_score,
                                    float* db_score, const xv_act* dfused, void* workspace, size_t workspace_bytes,
@@ -812,18 +815,21 @@ extern "C" int xv_decoder_head_bwd(const xv_act* fused, const float* w_score, co
                dfused && dfused->data && workspace);
   XV_CHECK_SHAPE(fused->c > 0 && (fused->c & 7) == 0 && fused->c <= 256 && num_classes >= 1 && num_classes <= 32);
   XV_CHECK_SHAPE(dfused->n == fused->n && dfused->h == fused->h && dfused->w == fused->w && dfused->c == fused->c);
-  if (workspace_bytes < xv_decoder_head_bwd_workspace_bytes(fused->n, fused->h, fused->w, num_classes)) return XV_EWORKSPACE;
-  XV_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
-  hipStream_t s = (hipStream_t)stream;
   const int CM = (num_classes + 3) / 4 * 4;
-  float* S = (float*)workspace;
-  float* dscore = S + (size_t)fused->n * (fused->h + 2) * (fused->w + 2) * CM;
-  int rc = xv_score_lowres(fused, w_score, num_classes, S, stream);
-  if (rc != XV_OK) return rc;
+  // 160 KB a workgroup: U = 256 takes CM <= 16, CM = 32 takes U <= 200.  Refused HERE, before the first launch -- the
+  // loss kernel and its reduce add into *loss and db_score, and the third launch would fail behind them.
+  XV_CHECK_SHAPE(head_bwd_lds_bytes(fused->c, CM) <= (size_t)160 * 1024);
   const int64_t npix = (int64_t)fused->n * fused->h * fused->w * 64;
   const int64_t lowres = (int64_t)fused->n * fused->h * fused->w;
   const int64_t ncols = lowres * 8;  // columns of eight output pixels
   XV_CHECK_SHAPE(npix < 0x7fff0000);
+  if (workspace_bytes < xv_decoder_head_bwd_workspace_bytes(fused->n, fused->h, fused->w, num_classes)) return XV_EWORKSPACE;
+  XV_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
+  hipStream_t s = (hipStream_t)stream;
+  float* S = (float*)workspace;
+  float* dscore = S + (size_t)fused->n * (fused->h + 2) * (fused->w + 2) * CM;
+  int rc = xv_score_lowres(fused, w_score, num_classes, S, stream);
+  if (rc != XV_OK) return rc;
   const unsigned g1 = (unsigned)((ncols + 255) / 256 < 4096 ? (ncols + 255) / 256 : 4096), g2 = (unsigned)((lowres + 255) / 256);
   const int U = fused->c;
   float* dws_part = dscore + (size_t)lowres * 24 * CM;  // g2 slabs of U x CM partial sums (U <= 256: sized by the query above)
@@ -840,7 +846,7 @@ extern "C" int xv_decoder_head_bwd(const xv_act* fused, const float* w_score, co
     hipLaunchKernelGGL(partials_reduce_kernel<256>, dim3(CMV + 1), dim3(256), 0, s, (const float*)loss_part,          \
                        (int)g1, CMV + 1,                                                                              \
                        db_score, num_classes, loss, CMV);                                                             \
-    const size_t lds = (size_t)(U * CMV + 256 * CMV) * 4 + (size_t)256 * U * 2;                                       \
+    const size_t lds = head_bwd_lds_bytes(U, CMV);                                                                    \
     static bool attr[XV_MAX_DEVICES] = {false};                                                                      \
     {                                                                                                                \
       const hipError_t e =                                                                                           \
