@@ -483,6 +483,30 @@ int xv_fused_head_fwd(const float* Sa, const float* Sb, const float* bias_a, con
                       int num_classes, int mode, const float* tab, const float* lognorm, const float* logprior,
                       int64_t* fused_label, void* stream);
 
+/* Grid-scoring form of the Dirichlet fused head (experiments/different_evaluation_parameters.py:10-61 on one pass of the
+ * trunks): Sa, Sb, biases, n, hi, wi, num_classes as xv_fused_head_fwd takes them; num_points parameter sets G, each as that
+ * function's mode 1 takes one: tab float [G][2][C][C] (alpha-1), lognorm [G][2][C], logprior [G][C].  Every output pixel is
+ * fused under all G sets -- the label of point g is the one xv_fused_head_fwd gives with point g's tables, bit for bit -- and
+ * cm int64 [G][C][C] (rows = ground truth) counts it as xv_confusion_matrix would against labels int32 [n][8hi][8wi]:
+ * accumulated, not cleared; no label map is written.  max_workgroups bounds the grid (0: the kernel's own bound).  XV_EINVAL
+ * for a null pointer, num_classes < 2, num_points < 1 or num_points above xv_fused_head_grid_capacity(num_classes).        */
+int xv_fused_head_grid_score_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                                 int wi, int num_classes, int num_points, const float* tab, const float* lognorm,
+                                 const float* logprior, const int32_t* labels, int64_t* cm, int max_workgroups, void* stream);
+
+/* Most parameter sets one xv_fused_head_grid_score_fwd launch takes at this class count (its tables and counters share one
+ * workgroup's LDS): at least 16 at 12 classes, at least 1 at 32; 0 outside 2..32 classes.  No GPU call.                    */
+int xv_fused_head_grid_capacity(int num_classes);
+
+/* Joint label histogram of a two-expert Bayes fusion: both experts' labels as xv_fused_head_fwd's mode 0 takes them
+ * (bits of xv_decoder_head_fwd's label) -> hist int64 [C][C][C], hist[label][a][b] += 1 over the pixels with 0 <= label < C
+ * (labels int32 [n][8hi][8wi], 16-byte aligned): accumulated, not cleared.  A Bayes-fused label is a function of (a, b)
+ * alone, so the histogram gives the confusion matrix of every class prior on the host.  XV_EINVAL for a null pointer,
+ * num_classes < 2 or num_classes > 20 (the counters of one workgroup: 32 KB of LDS).                                        */
+int xv_fused_head_joint_hist_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                                 int wi, int num_classes, const int32_t* labels, int64_t* hist, int max_workgroups,
+                                 void* stream);
+
 /* Variance head of the MC-dropout fusion model (variance_mix.py:7-15,33-83): Sa / Sb = xv_score_lowres of each expert's
  * (T+1) n-image map (slot 0 plain, slots 1..T dropout samples; T = num_samples) -> per output pixel and expert the softmax of
  * every pass, the variance over the T samples averaged over the classes, and the certainty-weighted fusion of the plain

@@ -111,6 +111,9 @@ SIGNATURES = {
     'xv_count_valid_labels': (_i, [_vp, _i, _i64, _vp, _vp]),
     'xv_score_lowres': (_i, [_actp, _vp, _i, _vp, _vp]),
     'xv_fused_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'xv_fused_head_grid_score_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'xv_fused_head_grid_capacity': (_i, [_i]),
+    'xv_fused_head_joint_hist_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'xv_variance_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'xv_mc_uncertainty_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xv_mc_uncertainty_score_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,10 @@
 """FusionModel base + test_pipeline (reference: xview/models/basic_fusion_model.py)."""
+from copy import deepcopy
+
+import numpy as np
 import torch
 
-from .base_model import BaseModel
+from .base_model import BaseModel, iterate_batches, score_measures
 from .fcn import FcnEngine, init_variables
 
 
@@ -183,16 +186,91 @@ def fused_head_applicable(model):
     return all(isinstance(e, FcnEngine) and e.commuted_head() for e in model.experts.values())
 
 
-def run_fused_head(model, batch, tab, logprior, lognorm=None):
-    """Both trunks (run_trunks) up to their low-resolution class scores, then ONE kernel: per-pixel logits, softmax / argmax
-    per expert and the Bayes or Dirichlet fusion -> fused labels."""
+def run_lowres_scores(model, batch):
+    """Both trunks (run_trunks) up to their low-resolution class scores: (Sa, Sb, bias_a, bias_b, n, hi, wi), what the fused
+    heads take."""
     inputs = {m: model._to_device(batch[m], torch.float32) for m in model.modalities}
     res = run_trunks(model, inputs, lambda m, st: model.experts[m].lowres_scores(inputs[m], st=st))
     a, b = model.modalities
     S, geo = {m: r[0] for m, r in res.items()}, res[a][1]
+    return S[a], S[b], model.experts[a].b['score'], model.experts[b].b['score'], geo[0], geo[1], geo[2]
+
+
+def run_fused_head(model, batch, tab, logprior, lognorm=None):
+    """Both trunks (run_trunks) up to their low-resolution class scores, then ONE kernel: per-pixel logits, softmax / argmax
+    per expert and the Bayes or Dirichlet fusion -> fused labels."""
     from . import ops
-    return ops.fused_head(S[a], S[b], model.experts[a].b['score'], model.experts[b].b['score'], geo[0], geo[1], geo[2],
-                          model.config['num_classes'], tab, logprior, lognorm=lognorm)
+    Sa, Sb, ba, bb, n, hi, wi = run_lowres_scores(model, batch)
+    return ops.fused_head(Sa, Sb, ba, bb, n, hi, wi, model.config['num_classes'], tab, logprior, lognorm=lognorm)
+
+
+# ---- grid search over the fusion parameters in ONE pass of the experts (experiments/different_evaluation_parameters.py) ------
+# The reference builds and evaluates one model per grid point.  The parameters of the fusion itself (class prior, sigma, the
+# regularisation of the Dirichlet fit) never reach the experts, so a fusion model scores all of them on one pass: the experts
+# run once per batch and only the fusion and the counting are repeated -- inside one kernel where the fused head serves the
+# model (score_grid_fused), through the fusion kernels on the experts' materialised outputs otherwise (score_grid_generic).
+# Both count the same integers.  The pass runs eagerly (no hipGraph capture: it is not the step predict() replays).
+
+def parameter_combinations(search_parameters, net_config):
+    """Every combination of the searched values as a full config: copies of `net_config` with the searched keys replaced.
+    The FIRST key of `search_parameters` varies slowest, the last one fastest."""
+    configs = [net_config]
+    for key, values in search_parameters.items():
+        configs = [dict(deepcopy(config), **{key: value}) for config in configs for value in values]
+    return configs
+
+
+def grid_point_configs(model, search_parameters, searchable):
+    """parameter_combinations over the model's own config, after refusing what one pass cannot vary: any key outside
+    `searchable` changes the experts or the data flow and needs a model per grid point (experiments.grid_search)."""
+    for key in search_parameters:
+        if key not in searchable:
+            raise ValueError('score_grid of %s cannot search %r in one pass (searchable: %s); build one model per grid point '
+                             'with experiments.grid_search' % (type(model).__name__, key, ', '.join(searchable)))
+    return parameter_combinations(search_parameters, model.config)
+
+
+def _labelled_batches(model, data, max_iterations):
+    for batch in model._device_batches(iterate_batches(data, model.config['batchsize'], max_iterations), labels=True):
+        yield batch, model._to_device(batch['labels'], torch.int32)
+
+
+def score_grid_fused(model, data, counts, count_batch, max_iterations=None):
+    """The fused route: per batch both trunks once (run_lowres_scores), then count_batch(Sa, Sb, bias_a, bias_b, n, hi, wi,
+    labels, counts) accumulates into the device tensor `counts`."""
+    for batch, labels in _labelled_batches(model, data, max_iterations):
+        count_batch(*run_lowres_scores(model, batch), labels, counts)
+    return counts
+
+
+def score_grid_generic(model, data, num_points, wants, fuse_point, max_iterations=None):
+    """The generic route (any experts, any number of them): per batch every expert once (run_experts), then per grid point g
+    fuse_point(expert outputs, g) -> fused labels, counted by ops.confusion_matrix.  Returns the int64 [G, C, C] counts."""
+    from . import ops
+    C = model.config['num_classes']
+    counts = torch.zeros((num_points, C, C), dtype=torch.int64, device=model.device)
+    for batch, labels in _labelled_batches(model, data, max_iterations):
+        outs = run_experts(model, batch, wants)
+        for g in range(num_points):
+            ops.confusion_matrix(labels, fuse_point(outs, g).contiguous(), counts[g])
+    return counts
+
+
+def reduce_grid_counts(model, counts):
+    """Sum the counts over the ranks as score() sums its matrix (config reduce_score_over_ranks)."""
+    if model.config.get('reduce_score_over_ranks', False):
+        from .parallel import allreduce_sum_
+        allreduce_sum_(counts)
+    return counts
+
+
+def grid_results(configs, confusion_matrices):
+    """[(point config, measures, confusion matrix float64 [C, C])] per grid point, each pair as score() returns it."""
+    out = []
+    for config, cm in zip(configs, confusion_matrices):
+        cm = np.asarray(cm).astype(np.float64)
+        out.append((config, score_measures(cm), cm))
+    return out
 
 
 class FusionModel(BaseModel):

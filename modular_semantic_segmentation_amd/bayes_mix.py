@@ -5,7 +5,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .basic_fusion_model import FusionModel, fused_head_applicable, run_fused_head
+from .basic_fusion_model import (FusionModel, fused_head_applicable, grid_point_configs, grid_results, reduce_grid_counts,
+                                 run_fused_head, score_grid_fused, score_grid_generic)
 
 UNIFORM_PRIOR = 1.0 / 14     # the reference hard-codes 1/14 regardless of num_classes (bayes_mix.py:42,95)
 
@@ -68,6 +69,25 @@ def bayes_decision_matrix(confusion_matrices, class_prior='data'):
     return fused.reshape([num_classes for _ in range(num_experts)])
 
 
+def fused_decision_table(loglik, logprior):
+    """dec[a][b] = argmax_k ((loglik[0][a][k] + loglik[1][b][k]) + logprior[k]), lowest index on ties: the table the fused
+    Bayes head builds in LDS from float32 tables, with its float32 sums in its order (bayes_decision_matrix is the float64
+    form of the decision_matrix=True path; the two may differ where two classes tie within float32)."""
+    loglik, logprior = np.asarray(loglik, np.float32), np.asarray(logprior, np.float32)
+    with np.errstate(invalid='ignore'):
+        total = (loglik[0][:, None, :] + loglik[1][None, :, :]) + logprior
+    return np.argmax(total, axis=-1)
+
+
+def confusion_from_joint_hist(hist, decision):
+    """cm[l][decision[a][b]] += hist[l][a][b]: the confusion matrix of a fusion that decides by the experts' label pair."""
+    C = hist.shape[0]
+    cm = np.zeros((C, C), hist.dtype)
+    for k in range(C):
+        cm[:, k] = hist[:, decision == k].sum(-1)
+    return cm
+
+
 class BayesFusion(FusionModel):
     """config: num_units, num_classes (via data_description), prefixes, num_channels, expert_model,
     class_prior ('data' | 'uniform' | float), confusion_matrices {modality: [C,C] label x pred};
@@ -121,3 +141,40 @@ class BayesFusion(FusionModel):
         if output_attr in ('probs', 'prob'):
             return torch.stack([self.probs[m] for m in self.modalities], 1)
         return fused
+
+    # ---- grid search over the class prior on one pass of the experts ------------------------------------
+    searchable = ('class_prior',)
+    JOINT_HIST_MAX_CLASSES = 20         # xv_fused_head_joint_hist_fwd: C^3 u32 counters in one workgroup's LDS
+
+    def score_grid(self, data, search_parameters, max_iterations=None):
+        """score() under every `class_prior` of `search_parameters` on ONE pass of the experts over `data`: [(point config,
+        measures, confusion matrix)] in parameter_combinations order, each pair what score() of a model with that config
+        returns.  A Bayes-fused label is a function of the experts' label pair, so where the fused head serves the model the
+        pass only counts the joint histogram of (ground truth, label a, label b) and every prior's matrix follows on the host."""
+        configs = grid_point_configs(self, search_parameters, self.searchable)
+        mats = [self.confusion_matrices[m] for m in self.modalities]
+        C = self.config['num_classes']
+        lut = self.config.get('decision_matrix', False)
+        if not lut and fused_head_applicable(self) and C <= self.JOINT_HIST_MAX_CLASSES:
+            hist = torch.zeros((C, C, C), dtype=torch.int64, device=self.device)
+
+            def count_batch(Sa, Sb, ba, bb, n, hi, wi, labels, hist):
+                ops.fused_head_joint_hist(Sa, Sb, ba, bb, n, hi, wi, C, labels, hist=hist)
+            score_grid_fused(self, data, hist, count_batch, max_iterations)
+            hist = reduce_grid_counts(self, hist).cpu().numpy()
+            counts = [confusion_from_joint_hist(hist, fused_decision_table(*bayes_tables(mats, c['class_prior'])))
+                      for c in configs]
+            return grid_results(configs, counts)
+        if lut and len(self.modalities) == 2:
+            luts = [torch.from_numpy(bayes_decision_matrix(mats, c['class_prior']).astype(np.int64)).to(self.device)
+                    for c in configs]
+
+            def fuse_point(outs, g):
+                return ops.bayes_fuse_lut(*[outs[m]['classification'] for m in self.modalities], luts[g])
+        else:
+            tables = [tuple(torch.from_numpy(t).to(self.device) for t in bayes_tables(mats, c['class_prior'])) for c in configs]
+
+            def fuse_point(outs, g):
+                return ops.bayes_fuse([outs[m]['classification'] for m in self.modalities], *tables[g])[0]
+        counts = score_grid_generic(self, data, len(configs), ('classification',), fuse_point, max_iterations)
+        return grid_results(configs, reduce_grid_counts(self, counts).cpu().numpy())

@@ -902,6 +902,221 @@ __global__ __launch_bounds__(256) void fused_dirichlet_head_pk_kernel(const floa
   }
 }
 
+// ---- grid-scoring heads (experiments/different_evaluation_parameters.py:10-61: one evaluate() per grid point) --------------
+// The searched fusion parameters (sigma, class_prior, delta, beta) never reach the trunks: they only change the small tables
+// the fused head reads.  So the trunks run once per batch and these kernels score every pixel under ALL parameter sets, counting
+// straight into confusion matrices in LDS: no label map, probability map or per-point intermediate reaches HBM.
+//
+// One wave's keys -> LDS counters.  Neighbouring pixels agree on (label, prediction), so up to 64 lanes of a wave would meet on
+// one counter; equal keys are aggregated first: the lowest pending lane's key is broadcast, the lanes holding it are counted by
+// a ballot, that lane alone adds the count, and the loop runs once per DISTINCT key of the wave (one to three on segmentation
+// maps, at most 64).  Exact whatever the keys are, and it needs no table copies, which is what leaves the LDS to the grid
+// points.  key < 0: nothing to count.  Every lane of the wave calls it, in converged control flow.
+__device__ __forceinline__ void xv_wave_count(uint32_t* cells, int key) {
+  unsigned long long todo = __ballot(key >= 0);
+  const int lane = (int)__lane_id();
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int k0 = __builtin_amdgcn_readlane(key, leader);
+    const unsigned long long same = __ballot(key == k0);
+    if (lane == leader) atomicAdd(&cells[k0], (uint32_t)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+// Dirichlet: per pixel ONCE both experts' log(1e-20 + p) -- head_load_taps / head_eval_taps / head_max / head_softmax and the
+// renormalisation lines of fused_head_kernel<CM, 1>, statement for statement -- then per grid point g the C dot products (the
+// ascending-k fmaf chain of dirichlet_fuse_kernel, two classes per v_pk_fma_f32 on the transposed table as in the fused head),
+// - lognorm, expert 0 + expert 1, + logprior, first-maximum argmax: the label xv_fused_head_fwd gives with point g's tables,
+// bit for bit.  cm[g][label][pred] += 1 for the pixels xv_confusion_matrix counts (0 <= label < C).  LDS: per point the tables
+// [2][CM k][CM c], lognorm [2][CM], logprior [CM], then u32 counters [G][C][C].  A bounded grid, pixels in a grid-stride loop
+// whose trip count is uniform over the workgroup (xv_wave_count needs whole waves; a lane past the end recomputes the last
+// pixel and counts nothing), one 64-bit global atomic per non-zero cell and workgroup.
+template <int CM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 4 : 1))) void fused_head_grid_score_kernel(const float* __restrict__ Sa, const float* __restrict__ Sb,
+                                                                   const float* __restrict__ ba, const float* __restrict__ bb,
+                                                                   int N, int Hi, int Wi, int C, int G,
+                                                                   const float* __restrict__ tab_g,
+                                                                   const float* __restrict__ lognorm_g,
+                                                                   const float* __restrict__ logprior_g,
+                                                                   const int32_t* __restrict__ labels,
+                                                                   unsigned long long* __restrict__ cm) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  constexpr int PT = 2 * CM * CM + 3 * CM;  // floats per grid point
+  extern __shared__ __attribute__((aligned(16))) float gs_tab[];
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(gs_tab + G * PT);
+  for (int i = threadIdx.x; i < G * PT; i += 256) {
+    const int g = i / PT, r = i - g * PT;
+    float v;
+    if (r < 2 * CM * CM) {
+      const int c = r % CM, k = (r / CM) % CM, e = r / (CM * CM);
+      v = (c < C && k < C) ? tab_g[((g * 2 + e) * C + c) * C + k] : 0.f;
+    } else if (r < 2 * CM * CM + 2 * CM) {
+      const int q = r - 2 * CM * CM, k = q % CM, e = q / CM;
+      v = k < C ? lognorm_g[(g * 2 + e) * C + k] : 0.f;
+    } else {
+      const int k = r - 2 * CM * CM - 2 * CM;
+      v = k < C ? logprior_g[g * C + k] : 0.f;
+    }
+    gs_tab[i] = v;
+  }
+  for (int i = threadIdx.x; i < G * C * C; i += 256) cnt[i] = 0u;
+  __syncthreads();
+  const int Ho = Hi * 8, Wo = Wi * 8;
+  const int64_t npix = (int64_t)N * Ho * Wo;
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < npix; base += (int64_t)gridDim.x * 256) {
+    const bool live = base + threadIdx.x < npix;
+    if (__ballot(live) == 0) continue;  // (wave-uniform)
+    const int64_t opix = live ? base + threadIdx.x : npix - 1;
+    const int ox = (int)(opix % Wo);
+    const int oy = (int)((opix / Wo) % Ho);
+    const int n = (int)(opix / ((int64_t)Wo * Ho));
+    int iy1, ix1;
+    float wy1, wy0, wx1, wx0;
+    bilinear_taps<8>(oy, iy1, wy1, wy0);
+    bilinear_taps<8>(ox, ix1, wx1, wx0);
+    f32x2 lg[2][CM / 2];  // log(1e-20 + p) of both experts, class pairs (the splat of one class is an operand modifier)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      // the second expert's taps are requested after the first one's arithmetic (its address waits for a result of it: an
+      // empty asm, no instruction): both sets of taps at once are 8 CM registers, and the scheduler does ask for them together
+      int ne = n;
+      if (e == 1) asm volatile("" : "+v"(ne) : "v"(lg[0][CM / 2 - 1].y));
+      f32x4 ta[CM / 4], tb[CM / 4], tc[CM / 4], td[CM / 4];
+      head_load_taps<CM>(e == 0 ? Sa : Sb, ne, iy1, ix1, Hi, Wi, ta, tb, tc, td);
+      float sc[CM];
+      head_eval_taps<CM>(ta, tb, tc, td, wy1, wy0, wx1, wx0, e == 0 ? ba : bb, C, sc);
+      const float m = head_max<CM>(sc, C);
+      head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < CM; ++k) {
+        sc[k] = k < C ? sc[k] : 0.f;
+        sum += sc[k];
+      }
+      const float rs = xv_fast_rcp(sum);
+#pragma unroll
+      for (int k = 0; k < CM; ++k) sc[k] = k < C ? xv_fast_log(1e-20f + sc[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
+#pragma unroll
+      for (int k2 = 0; k2 < CM / 2; ++k2) lg[e][k2] = f32x2{sc[2 * k2], sc[2 * k2 + 1]};
+    }
+    const int l = live ? labels[opix] : -1;
+    const bool valid = l >= 0 && l < C;
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      const float* tg = gs_tab + g * PT;
+      const float* ln = tg + 2 * CM * CM;
+      const float* lp = ln + 2 * CM;
+      // four classes at a time, both experts' dot products side by side: nothing of size CM but lg stays live
+      float best = 0.f;
+      int bi = 0;
+#pragma unroll
+      for (int c4 = 0; c4 < CM / 4; ++c4) {
+        f32x2 dot2[2][2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          dot2[e][0] = dot2[e][1] = f32x2{0.f, 0.f};
+#pragma unroll
+          for (int k = 0; k < CM; ++k) {
+            const f32x4 r = *reinterpret_cast<const f32x4*>(tg + (e * CM + k) * CM + 4 * c4);
+            const f32x2 lk = (k & 1) ? lg[e][k >> 1].yy : lg[e][k >> 1].xx;
+            dot2[e][0] = __builtin_elementwise_fma(f32x2{r.x, r.y}, lk, dot2[e][0]);
+            dot2[e][1] = __builtin_elementwise_fma(f32x2{r.z, r.w}, lk, dot2[e][1]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = 4 * c4 + j;
+          const float L0 = dot2[0][j >> 1][j & 1] - ln[c];
+          const float L1 = dot2[1][j >> 1][j & 1] - ln[CM + c];
+          const float total = L0 + L1;
+          const float v = total + lp[c];
+          if (c < C && (c == 0 || v > best)) {
+            best = v;
+            bi = c;
+          }
+        }
+      }
+      xv_wave_count(cnt + g * C * C, valid ? l * C + bi : -1);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < G * C * C; i += 256) {
+    const uint32_t v = cnt[i];
+    if (v) atomicAdd(&cm[i], (unsigned long long)v);
+  }
+}
+
+// Bayes: a fused label is a function of the two experts' labels alone, so ONE joint histogram hist[label][a][b] gives every
+// grid point's confusion matrix on the host (cm_g[l][dec_g[a][b]] += hist[l][a][b]); its marginals are the experts' own
+// matrices.  The experts' labels as in fused_head_kernel<CM, 0>: head_label_fast, head_softmax when it returns -1, P
+// consecutive output pixels per thread on shared taps: four up to 12 classes, two above (four pixels' scores beside the 4 CM
+// registers of the taps leave the four waves per SIMD at 16 classes).  u32 counters [C][C][C] in LDS (32 KB at 20 classes), the
+// grid and the flush of the kernel above.
+constexpr int xv_joint_hist_pixels(int cm) { return cm <= 12 ? 4 : 2; }
+template <int CM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 4 : 1))) void fused_head_joint_hist_kernel(const float* __restrict__ Sa, const float* __restrict__ Sb,
+                                                                   const float* __restrict__ ba, const float* __restrict__ bb,
+                                                                   int N, int Hi, int Wi, int C,
+                                                                   const int32_t* __restrict__ labels,
+                                                                   unsigned long long* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t jh_cnt[];  // [C][C][C]
+  const int cells = C * C * C;
+  for (int i = threadIdx.x; i < cells; i += 256) jh_cnt[i] = 0u;
+  __syncthreads();
+  constexpr int P = xv_joint_hist_pixels(CM);
+  const int Ho = Hi * 8, Wo = Wi * 8, Wq = Wo / P;
+  const int64_t nquads = (int64_t)N * Ho * Wq;
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < nquads; base += (int64_t)gridDim.x * 256) {
+    const bool live = base + threadIdx.x < nquads;
+    if (__ballot(live) == 0) continue;  // (wave-uniform)
+    const int64_t quad = live ? base + threadIdx.x : nquads - 1;
+    const int ox0 = (int)(quad % Wq) * P;
+    const int oy = (int)((quad / Wq) % Ho);
+    const int n = (int)(quad / ((int64_t)Wq * Ho));
+    int iy1, ix1;
+    float wy1, wy0;
+    bilinear_taps<8>(oy, iy1, wy1, wy0);
+    {
+      float u1, u0;
+      bilinear_taps<8>(ox0, ix1, u1, u0);
+    }
+    int lab[2][P];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      // (the second expert's taps wait for the first one's labels, as in the kernel above)
+      int ne = n;
+      if (e == 1) asm volatile("" : "+v"(ne) : "v"(lab[0][P - 1]));
+      f32x4 ta[CM / 4], tb[CM / 4], tc[CM / 4], td[CM / 4];
+      head_load_taps<CM>(e == 0 ? Sa : Sb, ne, iy1, ix1, Hi, Wi, ta, tb, tc, td);
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        int ixp;
+        float wx1, wx0;
+        bilinear_taps<8>(ox0 + p, ixp, wx1, wx0);
+        float sc[CM];
+        head_eval_taps<CM>(ta, tb, tc, td, wy1, wy0, wx1, wx0, e == 0 ? ba : bb, C, sc);
+        const float m = head_max<CM>(sc, C);
+        int l = head_label_fast<CM>(sc, m, C);
+        if (l < 0) l = head_softmax<CM>(sc, m, C);
+        lab[e][p] = l;
+      }
+    }
+    typedef int i32xP __attribute__((ext_vector_type(P)));
+    const i32xP lv = *reinterpret_cast<const i32xP*>(labels + quad * P);
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const int l = lv[p];
+      xv_wave_count(jh_cnt, (live && l >= 0 && l < C) ? (l * C + lab[0][p]) * C + lab[1][p] : -1);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < cells; i += 256) {
+    const uint32_t v = jh_cnt[i];
+    if (v) atomicAdd(&hist[i], (unsigned long long)v);
+  }
+}
+
 // ---- softmax + argmax on dense fp32 scores (basic_fusion_model.py:21-22) -------------------------
 template <int CMAX>
 __global__ __launch_bounds__(256) void softmax_argmax_kernel(const float* __restrict__ score, int64_t npix, int C,
@@ -1144,6 +1359,66 @@ extern "C" int xv_fused_head_fwd(const float* Sa, const float* Sb, const float* 
   }
   XV_CM_SWITCH(num_classes, XV_FH)
 #undef XV_FH
+  return xv_launch_status();
+}
+
+// Grid-scoring heads (see fused_head_grid_score_kernel / fused_head_joint_hist_kernel).  LDS of one launch: 40 KB, so that four
+// 256-thread workgroups share a CU's 160 KB (the four waves per SIMD of the register budget); one grid point takes its tables
+// and its [C][C] u32 counters.
+static const size_t XV_GRID_SCORE_LDS = 40 * 1024;
+static size_t grid_point_bytes(int num_classes) {
+  const size_t cm = (size_t)(num_classes + 3) / 4 * 4;
+  return (2 * cm * cm + 3 * cm + (size_t)num_classes * num_classes) * 4;
+}
+
+extern "C" int xv_fused_head_grid_capacity(int num_classes) {
+  if (num_classes < 2 || num_classes > 32) return 0;
+  return (int)(XV_GRID_SCORE_LDS / grid_point_bytes(num_classes));
+}
+
+// workgroups of a grid-stride launch over `items` (256 per workgroup and step): four per CU, or the caller's bound
+static int grid_score_workgroups(int64_t items, int max_workgroups) {
+  const int grid = xv_grid_for(items, 256, xv_num_cus() * 4);
+  return max_workgroups > 0 && max_workgroups < grid ? max_workgroups : grid;
+}
+
+extern "C" int xv_fused_head_grid_score_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
+                                            int hi, int wi, int num_classes, int num_points, const float* tab,
+                                            const float* lognorm, const float* logprior, const int32_t* labels, int64_t* cm,
+                                            int max_workgroups, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && tab && lognorm && logprior && labels && cm);
+  XV_CHECK_ARG(num_classes >= 2 && num_points >= 1 && max_workgroups >= 0);
+  XV_CHECK_SHAPE(num_classes <= 32 && xv_dims_sane(n, hi, wi));
+  XV_CHECK_ARG(num_points <= xv_fused_head_grid_capacity(num_classes));
+  const int64_t npix = (int64_t)n * hi * wi * 64;
+  const int grid = grid_score_workgroups(npix, max_workgroups);
+  XV_CHECK_SHAPE(npix / grid < ((int64_t)1 << 31));  // (a workgroup's u32 counters)
+  const size_t lds = grid_point_bytes(num_classes) * num_points;
+  hipStream_t s = (hipStream_t)stream;
+#define XV_GS(CMV)                                                                                                          \
+  hipLaunchKernelGGL(fused_head_grid_score_kernel<CMV>, dim3(grid), dim3(256), lds, s, Sa, Sb, bias_a, bias_b, n, hi, wi,    \
+                     num_classes, num_points, tab, lognorm, logprior, labels, reinterpret_cast<unsigned long long*>(cm))
+  XV_CM_SWITCH(num_classes, XV_GS)
+#undef XV_GS
+  return xv_launch_status();
+}
+
+extern "C" int xv_fused_head_joint_hist_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
+                                            int hi, int wi, int num_classes, const int32_t* labels, int64_t* hist,
+                                            int max_workgroups, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && labels && hist && ((uintptr_t)labels & 15) == 0);
+  XV_CHECK_ARG(num_classes >= 2 && num_classes <= 20 && max_workgroups >= 0);  // 20^3 u32 counters: 32 KB of LDS
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  const int64_t nquads = (int64_t)n * hi * wi * 64 / xv_joint_hist_pixels((num_classes + 3) / 4 * 4);  // threads' pixel groups
+  const int grid = grid_score_workgroups(nquads, max_workgroups);
+  XV_CHECK_SHAPE(nquads / grid < ((int64_t)1 << 29));
+  const size_t lds = (size_t)num_classes * num_classes * num_classes * 4;
+  hipStream_t s = (hipStream_t)stream;
+#define XV_JH(CMV)                                                                                                          \
+  hipLaunchKernelGGL(fused_head_joint_hist_kernel<CMV>, dim3(grid), dim3(256), lds, s, Sa, Sb, bias_a, bias_b, n, hi, wi,    \
+                     num_classes, labels, reinterpret_cast<unsigned long long*>(hist))
+  XV_CM_SWITCH(num_classes, XV_JH)
+#undef XV_JH
   return xv_launch_status();
 }
 

@@ -8,7 +8,8 @@ from scipy.special import gammaln
 from . import ops
 from .base_model import BaseModel, iterate_batches
 from .basic_fusion_model import (calibrate_experts, engine_options, expert_factory, fused_head_applicable,  # noqa: F401
-                                 run_experts, run_fused_head, test_pipeline)
+                                 grid_point_configs, grid_results, reduce_grid_counts, run_experts, run_fused_head,
+                                 score_grid_fused, score_grid_generic, test_pipeline)
 from .dirichlet_fit import find_dirichlet_priors
 
 UNIFORM_PRIOR = 1.0 / 14     # dirichlet_mix.py:116
@@ -146,6 +147,12 @@ class DirichletFusion(BaseModel):
 
     def _fit_sufficient_statistic(self, counts, class_counts):
         """dirichlet_mix.py:207-257."""
+        self.dirichlet_params = self._dirichlet_em(counts, class_counts, self.config['delta'], self.config['beta'])
+        self.class_counts = class_counts
+        self._initialize_graph()       # rebuild the tables with the new measurements
+
+    def _dirichlet_em(self, counts, class_counts, delta, beta):
+        """{modality: [C,C] parameters} fitted to the sufficient statistics under one (delta, beta)."""
         C = self.config['num_classes']
 
         def dirichlet_em(measurements):
@@ -157,18 +164,61 @@ class DirichletFusion(BaseModel):
                 ss = (measurements[c, :] / class_counts[c]).astype('float64')
                 neg_ss = (measurements.sum(0) - measurements[c, :]) / (class_counts.sum() - class_counts[c])
                 params[:, c] = find_dirichlet_priors(ss, neg_ss, np.ones(C, 'float64'), max_iter=10000,
-                                                     delta=self.config['delta'], beta=self.config['beta'])
+                                                     delta=delta, beta=beta)
             return params
 
-        self.dirichlet_params = {m: dirichlet_em(counts[m]) for m in self.modalities}
-        self.class_counts = class_counts
-        self._initialize_graph()       # rebuild the tables with the new measurements
+        return {m: dirichlet_em(counts[m]) for m in self.modalities}
 
     def fit(self, data, *args, **kwargs):
         """Measure the experts against the ground truth of `data`, then fit the class-conditional
         Dirichlets (dirichlet_mix.py:259-273).  Returns {modality: [C,C], 'class_counts': [C]}."""
         modality_counts, class_counts = self._get_sufficient_statistic(data)
+        self.sufficient_statistics = (modality_counts, class_counts)      # what score_grid refits delta / beta from
         self._fit_sufficient_statistic(modality_counts, class_counts)
         ret = deepcopy(self.dirichlet_params)
         ret['class_counts'] = self.class_counts
         return ret
+
+    # ---- grid search over the fusion parameters on one pass of the experts ------------------------------
+    searchable = ('sigma', 'class_prior', 'delta', 'beta')
+
+    def _grid_tables(self, configs):
+        """Per grid point the (am1, lognorm, logprior) numpy tables dirichlet_tables gives a model of that config: sigma and
+        class_prior only rebuild them; a (delta, beta) other than this model's re-runs the host fit, once per distinct pair,
+        on the sufficient statistics of the last fit()."""
+        own = (self.config.get('delta'), self.config.get('beta'))
+        fitted = {}
+        for config in configs:
+            pair = (config.get('delta'), config.get('beta'))
+            if pair in fitted:
+                continue
+            if pair == own and hasattr(self, 'dirichlet_params'):
+                fitted[pair] = self.dirichlet_params
+            elif not hasattr(self, 'sufficient_statistics'):
+                raise UserWarning('ERROR: searching delta / beta needs the sufficient statistics of a fit(); call fit() first')
+            else:
+                fitted[pair] = self._dirichlet_em(*self.sufficient_statistics, delta=pair[0], beta=pair[1])
+        return [dirichlet_tables([fitted[(c.get('delta'), c.get('beta'))][m] for m in self.modalities], self.class_counts,
+                                 c['class_prior'], c['sigma']) for c in configs]
+
+    def score_grid(self, data, search_parameters, max_iterations=None):
+        """score() under every combination of `search_parameters` (lists of values for sigma, class_prior, delta, beta) on ONE
+        pass of the experts over `data`: [(point config, measures, confusion matrix)] in parameter_combinations order, each
+        pair what score() of a model with that config returns."""
+        configs = grid_point_configs(self, search_parameters, self.searchable)
+        if not hasattr(self, 'dirichlet_params') and not hasattr(self, 'sufficient_statistics'):
+            raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
+        tables = [tuple(torch.from_numpy(t).to(self.device) for t in point) for point in self._grid_tables(configs)]
+        C = self.config['num_classes']
+        if fused_head_applicable(self):
+            am1, lognorm, logprior = (torch.stack([point[i] for point in tables]).contiguous() for i in range(3))
+            counts = torch.zeros((len(configs), C, C), dtype=torch.int64, device=self.device)
+
+            def count_batch(Sa, Sb, ba, bb, n, hi, wi, labels, cm):
+                ops.fused_head_grid_score(Sa, Sb, ba, bb, n, hi, wi, C, am1, lognorm, logprior, labels, cm=cm)
+            score_grid_fused(self, data, counts, count_batch, max_iterations)
+        else:
+            def fuse_point(outs, g):
+                return ops.dirichlet_fuse([outs[m]['prob'] for m in self.modalities], *tables[g])[0]
+            counts = score_grid_generic(self, data, len(configs), ('prob',), fuse_point, max_iterations)
+        return grid_results(configs, reduce_grid_counts(self, counts).cpu().numpy())

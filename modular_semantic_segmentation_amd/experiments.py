@@ -1,6 +1,7 @@
 """The reference's evaluation / fusion experiment flows without the sacred experiment database
 (reference: experiments/evaluation.py:14-41,62-110, experiments/bayes_fusion.py:21-33,146-195,
-experiments/dirichlet_fusion.py:19-81, experiments/training.py, experiments/uncertainty_eval.py:18-52).
+experiments/dirichlet_fusion.py:19-81, experiments/training.py, experiments/uncertainty_eval.py:18-52,
+experiments/different_evaluation_parameters.py:10-61).
 
 Datasets here are dicts of arrays ({'rgb': [N,H,W,3], 'depth': [N,H,W,1], 'labels': [N,H,W]}) or any iterable of
 per-sample dicts (the data contract of base_model.iterate_batches); the reference's `tf.data` readers, the
@@ -12,6 +13,7 @@ from copy import deepcopy
 import numpy as np
 
 from . import get_model
+from .basic_fusion_model import parameter_combinations  # noqa: F401  (the reference's name, defined beside score_grid)
 from .bayes_mix import BayesFusion
 from .dirichlet_mix import DirichletFusion
 
@@ -129,3 +131,37 @@ def measure_metrics(net, data, metrics):
     for metric in metrics:
         ret[metric] = net.value_distribution(data, metric)
     return ret
+
+
+def _collect(results, values):
+    """Append every leaf of the (nested) dict `values` to the list under the same keys of `results`."""
+    for key, value in values.items():
+        if isinstance(value, dict):
+            _collect(results.setdefault(key, {}), value)
+        else:
+            results.setdefault(key, []).append(value)
+
+
+def grid_search(evaluation, search_parameters, net_config):
+    """experiments/different_evaluation_parameters.py:27-61: evaluation(config) -> (nested) dict of measurements, called once
+    per combination of `search_parameters` (lists of values; the first key varies slowest) on top of `net_config`.  Returns one
+    dict in which every config key and every measurement is a list over the grid points, nested measurement dicts merged key
+    by key.  One model per grid point: for the parameters of the fusion itself, grid_search_fusion takes one pass."""
+    results = {}
+    for config in parameter_combinations(search_parameters, net_config):
+        for key in config:                       # a config value is one entry, a dict among them
+            results.setdefault(key, []).append(config[key])
+        _collect(results, evaluation(config))
+    return results
+
+
+def grid_search_fusion(net, testset, search_parameters):
+    """grid_search's result for a fusion model's own parameters (DirichletFusion: sigma, class_prior, delta, beta;
+    BayesFusion: class_prior) from ONE pass of the experts over `testset` (net.score_grid): the config keys of `net` and the
+    measures of score() as lists over the grid points."""
+    results = {}
+    for config, measures, _ in net.score_grid(testset, search_parameters):
+        for key in config:
+            results.setdefault(key, []).append(config[key])
+        _collect(results, measures)
+    return results

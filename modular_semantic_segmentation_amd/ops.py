@@ -590,6 +590,74 @@ def fused_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, tab, logprior, lo
     return out
 
 
+def _check_lowres_pair(Sa, Sb, n, hi, wi, num_classes, labels):
+    cp = (int(num_classes) + 3) // 4 * 4
+    for name, S in (('Sa', Sa), ('Sb', Sb)):
+        _need(S, torch.float32, name)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %s of shape %s, expected %s' % (name, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+    _need(labels, torch.int32, 'labels')
+    if labels.numel() != n * hi * wi * 64:
+        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+
+
+def fused_head_grid_capacity(num_classes):
+    """Most grid points one xv_fused_head_grid_score_fwd launch takes at this class count."""
+    return int(_lib.lib().xv_fused_head_grid_capacity(int(num_classes)))
+
+
+def fused_head_grid_score(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, tab, lognorm, logprior, labels, cm=None,
+                          max_workgroups=0):
+    """Both experts' low-resolution scores, fused under G Dirichlet parameter sets at once (tab float32 [G,2,C,C] = alpha - 1,
+    lognorm [G,2,C], logprior [G,C], each set as fused_head takes one) and counted against labels (int32 [n, 8hi, 8wi]):
+    accumulates into cm (int64 [G,C,C], rows = ground truth; made here when None) and returns it.  More sets than one launch
+    holds (fused_head_grid_capacity) go in several launches on the same scores."""
+    C = int(num_classes)
+    _check_lowres_pair(Sa, Sb, n, hi, wi, C, labels)
+    for name, t in (('bias_a', bias_a), ('bias_b', bias_b), ('tab', tab), ('lognorm', lognorm), ('logprior', logprior)):
+        _need(t, torch.float32, name)
+    G = tab.shape[0]
+    if G < 1 or tuple(tab.shape) != (G, 2, C, C) or tuple(lognorm.shape) != (G, 2, C) or tuple(logprior.shape) != (G, C):
+        raise ValueError('tables of shapes %s, %s, %s, expected [G,2,C,C], [G,2,C], [G,C] with C = %d' % (
+            tuple(tab.shape), tuple(lognorm.shape), tuple(logprior.shape), C))
+    if cm is None:
+        cm = torch.zeros((G, C, C), dtype=torch.int64, device=Sa.device)
+    _need(cm, torch.int64, 'cm')
+    if tuple(cm.shape) != (G, C, C):
+        raise ValueError('cm of shape %s, expected %s' % (tuple(cm.shape), (G, C, C)))
+    cap = fused_head_grid_capacity(C)
+    if cap < 1:
+        raise ValueError('no grid-scoring head for %d classes' % C)
+    for g0 in range(0, G, cap):
+        g1 = min(G, g0 + cap)
+        rc = _lib.lib().xv_fused_head_grid_score_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C, g1 - g0,
+                                                    _ptr(tab[g0:g1]), _ptr(lognorm[g0:g1]), _ptr(logprior[g0:g1]), _ptr(labels),
+                                                    _ptr(cm[g0:g1]), int(max_workgroups), _stream())
+        _lib.check(rc, 'xv_fused_head_grid_score_fwd')
+    return cm
+
+
+def fused_head_joint_hist(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, hist=None, max_workgroups=0):
+    """Both experts' low-resolution scores -> the joint histogram of (ground truth, label of expert a, label of expert b):
+    accumulates into hist (int64 [C,C,C]; made here when None) over the pixels with a valid label and returns it.  At most 20
+    classes."""
+    C = int(num_classes)
+    _check_lowres_pair(Sa, Sb, n, hi, wi, C, labels)
+    _need(bias_a, torch.float32, 'bias_a')
+    _need(bias_b, torch.float32, 'bias_b')
+    if labels.data_ptr() & 15:            # (a slice of a larger map: the kernel reads label quads with 16-byte loads)
+        labels = labels.clone()
+    if hist is None:
+        hist = torch.zeros((C, C, C), dtype=torch.int64, device=Sa.device)
+    _need(hist, torch.int64, 'hist')
+    if tuple(hist.shape) != (C, C, C):
+        raise ValueError('hist of shape %s, expected %s' % (tuple(hist.shape), (C, C, C)))
+    rc = _lib.lib().xv_fused_head_joint_hist_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C, _ptr(labels),
+                                                _ptr(hist), int(max_workgroups), _stream())
+    _lib.check(rc, 'xv_fused_head_joint_hist_fwd')
+    return hist
+
+
 def variance_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, num_samples, want_score=False, want_probs=False,
                   want_variance=False):
     """Both experts' low-resolution scores of (num_samples + 1) * n images each (slot 0 plain, then the dropout samples) ->
