@@ -5,11 +5,13 @@ raises -- there is no CPU or PyTorch fallback.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libxview_hip.so')
 CSRC = os.path.join(_HERE, 'csrc')
+HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'xview_hip.h')
 
 
 class XvError(RuntimeError):
@@ -27,171 +29,71 @@ class xv_pack_desc(ctypes.Structure):
                 ('k', ctypes.c_int32), ('cin', ctypes.c_int32), ('cout', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
-_vp, _i, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-_actp = ctypes.POINTER(xv_act)
-_vpp = ctypes.POINTER(ctypes.c_void_p)
+_SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'size_t': ctypes.c_size_t,
+            'float': ctypes.c_float}
 
-# name -> (restype, argtypes); every symbol include/xview_hip.h declares
-SIGNATURES = {
-    'xv_version': (_i, []),
-    'xv_conv2d_choose_cfg': (_i, [_i] * 9),
-    'xv_conv_first_pair_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _actp, _actp, _vp]),
-    'xv_arch': (ctypes.c_char_p, []),
-    'xv_source_hash': (ctypes.c_char_p, []),
-    'xv_packed_weight_bytes': (ctypes.c_size_t, [_i, _i, _i]),
-    'xv_pack_conv_weights': (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    'xv_pack_conv_weights_pair': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    'xv_packed_weight_bytes_f8': (ctypes.c_size_t, [_i, _i, _i]),
-    'xv_pack_conv_weights_f8': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    'xv_conv2d_fwd': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _i, _vp]),
-    'xv_conv2d_fwd_cfg': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _i, _i, _vp]),
-    'xv_conv2d_fwd_pair': (_i, [_actp, _vp, _vp, _actp, _actp, _actp, _vp, _vp, _actp, _actp, _i, _vp]),
-    'xv_conv2d_num_cfgs': (_i, []),
-    'xv_conv2d_streamk_workspace_bytes': (ctypes.c_size_t, []),
-    'xv_conv2d_fwd_ws': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
-    'xv_conv2d_split_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
-    'xv_conv2d_fwd_split': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
-    'xv_conv2d_bwd_data_ws': (_i, [_actp, _vp, _vp, _actp, _actp, _actp, _i, _vp, ctypes.c_size_t, _vp]),
-    'xv_deconv_dense_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
-    'xv_deconv_dense_fwd': (_i, [_actp, _vp, _vp, _vp, _vp, _actp, _actp, _i, _i, _vp, ctypes.c_size_t, _vp]),
-    'xv_conv2d_first_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _actp, _i, _vp]),
-    'xv_conv2d_first_gather7s2_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _actp, _i, _vp]),
-    'xv_maxpool2x2_fwd': (_i, [_actp, _actp, _vp]),
-    'xv_upsample2x_relu_add': (_i, [_actp, _actp, _actp, _vp]),
-    'xv_upsample2x_affine_relu_add': (_i, [_actp, _vp, _vp, _actp, _actp, _vp]),
-    'xv_upsample2x_affine_act_add': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _vp]),
-    'xv_concat_channels': (_i, [_actp, _actp, _actp, _vp]),
-    'xv_dropout': (_i, [_actp, _actp, ctypes.c_float, ctypes.c_uint64, _vp]),
-    'xv_dropout_samples': (_i, [_actp, _actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
-    'xv_dropout_samples_inplace': (_i, [_actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
-    'xv_dropout_samples_only': (_i, [_actp, _actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
-    'xv_dropout_samples_only_inplace': (_i, [_actp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
-    'xv_conv2d_fwd_residual': (_i, [_actp, _vp, _vp, _actp, _actp, _i, _vp]),
-    'xv_subsample2': (_i, [_actp, _actp, _vp]),
-    'xv_gather_conv7s2': (_i, [_actp, _actp, _vp]),
-    'xv_im2col_dilated_pair': (_i, [_actp, _i, _i, _actp, _vp]),
-    'xv_subsample2_bwd': (_i, [_actp, _actp, _vp]),
-    'xv_gather_conv7s2_bwd': (_i, [_actp, _actp, _vp]),
-    'xv_conv_dilated_pair_fwd': (_i, [_actp, _vp, _vp, _i, _i, _i, _actp, _vp]),
-    'xv_im2col_dilated_pair_bwd': (_i, [_actp, _i, _i, _actp, _vp]),
-    'xv_add': (_i, [_actp, _actp, _actp, _vp]),
-    'xv_space_to_depth': (_i, [_actp, _i, _actp, _vp]),
-    'xv_space_to_depth_dense': (_i, [_vp, _i, _i, _actp, _vp]),
-    'xv_depth_to_space_dense': (_i, [_actp, _i, _i, _vp, _vp, _vp, _vp]),
-    'xv_act_to_dense_f32': (_i, [_actp, _vp, _vp]),
-    'xv_depth_to_space_dense_f32': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    'xv_decoder_head_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
-    'xv_decoder_head_fwd': (_i, [_actp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_decoder_head_affine_fwd': (_i, [_actp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    'xv_softmax_argmax': (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
-    'xv_bayes_fuse': (_i, [_vpp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_bayes_fuse_lut': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
-    'xv_dirichlet_fuse': (_i, [_vpp, _i, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_average_fuse': (_i, [_vpp, _i, _i, _i64, _vp, _vp]),
-    'xv_variance_fuse': (_i, [_vpp, _vpp, _i, _i, _i64, _vp, _vp, _vp]),
-    'xv_sampling_uncertainty': (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_pack_conv_weights_dgrad': (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    'xv_pack_conv_weights_multi': (_i, [_vp, _i, _vp]),
-    'xv_memset_zero': (_i, [_vp, ctypes.c_size_t, _vp]),
-    'xv_conv2d_bwd_data': (_i, [_actp, _vp, _vp, _actp, _actp, _actp, _i, _vp]),
-    'xv_conv2d_bwd_filter': (_i, [_actp, _actp, _vp, _vp, _i, _vp]),
-    'xv_set_wgrad_variant': (_i, [_i]),
-    'xv_conv2d_bwd_filter_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i]),
-    'xv_conv2d_bwd_filter_ws': (_i, [_actp, _actp, _vp, _vp, _i, _vp, ctypes.c_size_t, _vp]),
-    'xv_conv_dilated_pair_bwd_data': (_i, [_actp, _vp, _vp, _i, _i, _actp, _vp]),
-    'xv_conv_dilated_pair_bwd_filter_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
-    'xv_conv_dilated_pair_bwd_filter_ws': (_i, [_actp, _actp, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bias_grad': (_i, [_actp, _vp, _vp]),
-    'xv_conv2d_first_bwd_filter': (_i, [_vp, _i, _i, _i, _i, _actp, _vp, _vp, _vp]),
-    'xv_conv2d_first_bwd_filter_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
-    'xv_conv2d_first_bwd_filter_ws': (_i, [_vp, _i, _i, _i, _i, _actp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_maxpool2x2_bwd': (_i, [_actp, _actp, _actp, _vp]),
-    'xv_relu_bwd': (_i, [_actp, _actp, _actp, _vp]),
-    'xv_upsample2x_bwd': (_i, [_actp, _actp, _actp, _vp]),
-    'xv_count_valid_labels': (_i, [_vp, _i, _i64, _vp, _vp]),
-    'xv_score_lowres': (_i, [_actp, _vp, _i, _vp, _vp]),
-    'xv_fused_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    'xv_fused_head_grid_score_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    'xv_fused_head_grid_capacity': (_i, [_i]),
-    'xv_fused_head_joint_hist_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    'xv_variance_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    'xv_mc_uncertainty_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_mc_uncertainty_score_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    'xv_dropout_pixels_samples': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp]),
-    'xv_uncertainty_moments': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    'xv_uncertainty_dirichlet_head_fwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_uncertainty_dirichlet_fuse': (_i, [_vpp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_uncertainty_weights': (_i, [_vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_decoder_head_bwd_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
-    'xv_decoder_head_bwd': (_i, [_actp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _actp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_stats': (_i, [_actp, _vp, _vp]),
-    'xv_bn_finalize': (_i, [_vp, _i, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_bn_apply': (_i, [_actp, _vp, _vp, _i, _actp, _vp]),
-    'xv_bn_apply_ups8': (_i, [_actp, _vp, _vp, _i, _actp, _vp]),
-    'xv_score_dense_fwd_ups8': (_i, [_actp, _vp, _vp, _vp, _vp, _i, _actp, _vp, _vp]),
-    'xv_bn_bwd': (_i, [_actp, _actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _actp, _vp]),
-    'xv_bn_bwd_reduce': (_i, [_actp, _actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_bn_bwd_apply': (_i, [_actp, _actp, _actp, _vp, _vp, _vp, _vp, _i64, _actp, _vp]),
-    'xv_bn_bwd_reduce_zmask': (_i, [_actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_bwd_reduce_zmask_ups8': (_i, [_actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_workspace_bytes': (ctypes.c_size_t, [_i]),
-    'xv_conv2d_stats_rows': (_i, []),
-    'xv_conv2d_fwd_stats': (_i, [_actp, _vp, _vp, _actp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_sums_from_rows': (_i, [_vp, _i, _i, _vp, _vp]),
-    'xv_conv2d_route_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
-    'xv_conv2d_fwd_route': (_i, [_actp, _vp, _vp, _actp, _vp, ctypes.c_size_t, _vp]),
-    'xv_conv2d_bwd_data_route': (_i, [_actp, _vp, _vp, _vp, ctypes.c_size_t, _actp, _vp]),
-    'xv_bn_finalize_from_rows': (_i, [_vp, _i, _i, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _vp, _vp]),
-    'xv_bn_stats_finalize_ws': (_i, [_actp, _vp, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp,
-                                     _vp, _vp, _vp, _vp]),
-    'xv_bn_stats_finalize_ups8_ws': (_i, [_actp, _vp, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp,
-                                     _vp, _vp, _vp, _vp]),
-    'xv_bn_apply_pool': (_i, [_actp, _vp, _vp, _actp, _actp, _vp]),
-    'xv_bn_pool_bwd_reduce': (_i, [_actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_pool_bwd_apply': (_i, [_actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _actp, _vp]),
-    'xv_bn_stats_ws': (_i, [_actp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_stats_ups8_ws': (_i, [_actp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_bwd_reduce_ws': (_i, [_actp, _actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_dense_stats_ws': (_i, [_vp, _i64, _i, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_dense_bwd_reduce_ws': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_bn_bwd_apply_zmask': (_i, [_actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _actp, _vp]),
-    'xv_bn_bwd_apply_zmask_ups8': (_i, [_actp, _actp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _actp, _vp]),
-    'xv_bn_dense_bwd_reduce': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_bn_dense_bwd_apply': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-    'xv_bn_dense_stats': (_i, [_vp, _i64, _i, _vp, _vp]),
-    'xv_bn_dense_apply': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
-    'xv_bn_dense_bwd': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'xv_upsample_raw_fwd': (_i, [_actp, _i, _actp, _vp]),
-    'xv_upsample_raw_bwd': (_i, [_actp, _i, _actp, _vp]),
-    'xv_upsample_raw_bwd_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i, _i]),
-    'xv_upsample_raw_bwd_ws': (_i, [_actp, _i, _actp, _vp, ctypes.c_size_t, _vp]),
-    'xv_score_dense_fwd': (_i, [_actp, _vp, _vp, _i, _vp, _vp]),
-    'xv_softmax_ce_dense': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_softmax_ce_dense_affine': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_softmax_ce_dense_workspace_bytes': (ctypes.c_size_t, [_i64]),
-    'xv_softmax_ce_dense_ws': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'xv_score_dense_bwd': (_i, [_actp, _vp, _vp, _i, _vp, _vp, _actp, _vp]),
-    'xv_score_dense_bwd_workspace_bytes': (ctypes.c_size_t, [_i, _i, _i]),
-    'xv_score_dense_bwd_ws': (_i, [_actp, _vp, _vp, _i, _vp, _vp, _actp, _vp, ctypes.c_size_t, _vp]),
-    'xv_conv2d_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    'xv_conv2d_f32_pool': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    'xv_conv2d_f32_scalar': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    'xv_maxpool2x2_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    'xv_upsample2x_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    'xv_upsample2x_affine_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    'xv_decoder_head_affine_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    'xv_score_lowres_f32': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    'xv_decoder_head_from_scores': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    'xv_adam_step': (_i, [_vp, _vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                          ctypes.c_float, _vp]),
-    'xv_rmsprop_step': (_i, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
-    'xv_adagrad_step': (_i, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, _vp]),
-    'xv_dirichlet_suffstats': (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
-    'xv_confusion_matrix': (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
-    'xv_uncertainty_stats': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    'xv_narrow_labels': (_i, [_vp, _i64, _vp, _vp]),
-}
+
+def _ctype(ctext, decl, restype=False):
+    """The ctypes type of one C parameter or return type, by a closed map; anything else is an error, never a guess."""
+    words = re.findall(r'\w+|\*', ctext)
+    base = ' '.join(w for w in words if w not in ('const', '*'))
+    stars = words.count('*')
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and re.fullmatch(r'\w+', base):
+        if base == 'xv_act':
+            return ctypes.POINTER(xv_act)
+        return ctypes.c_char_p if restype and base == 'char' else ctypes.c_void_p
+    if stars == 2 and re.fullmatch(r'\w+', base):
+        return ctypes.POINTER(ctypes.c_void_p)              # a host array of device pointers
+    raise XvError('include/xview_hip.h: no ctypes mapping for %r in `%s`' % (ctext.strip(), decl))
+
+
+def parse_header(text):
+    """(functions, constants, structs) of the C header: name -> (restype, [argtypes]) for every declaration, name -> int for
+    every integer `#define XV_*`, name -> [(field, C type)] for every `typedef struct`.  Plain text processing: no
+    preprocessor, no compiler."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    constants = {m.group(1): int(m.group(2))
+                 for m in re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(XV_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', text, re.M)}
+    structs = {}
+    struct = re.compile(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;', re.S)
+    for name, body in struct.findall(text):
+        fields = structs[name] = []
+        for member in filter(None, (' '.join(f.split()) for f in body.split(';'))):
+            m = re.fullmatch(r'(.*?[\s*])(\w+(?:\s*,\s*\w+)*)', member)        # type, then one or more names
+            if not m:
+                raise XvError('include/xview_hip.h: cannot parse member `%s` of %s' % (member, name))
+            fields += [(field.strip(), m.group(1).replace(' *', '*').strip()) for field in m.group(2).split(',')]
+    text = struct.sub(' ', text)
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)                  # include guards, includes, defines
+    text = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', ' ', text, flags=re.M)
+    functions = {}
+    for decl in filter(None, (' '.join(d.split()) for d in text.split(';'))):
+        m = re.fullmatch(r'([\w\s*]+?)\s*\b(\w+)\s*\(([^()]*)\)', decl)
+        if not m or m.group(2) in functions:
+            raise XvError('include/xview_hip.h: not a function declaration, or declared twice: `%s`' % decl)
+        params = [] if m.group(3).strip() == 'void' else m.group(3).split(',')
+        args = []
+        for p in params:
+            pm = re.fullmatch(r'\s*(.*?[\s*])(\w+)\s*', p)               # type, then the parameter's name
+            if not pm:
+                raise XvError('include/xview_hip.h: cannot parse parameter `%s` of `%s`' % (p.strip(), decl))
+            args.append(_ctype(pm.group(1), decl))
+        functions[m.group(2)] = (_ctype(m.group(1), decl, restype=True), args)
+    return functions, constants, structs
+
+
+def _read_header():
+    if not os.path.exists(HEADER):
+        raise XvError('%s not found: the ctypes table is derived from it' % HEADER)
+    with open(HEADER) as f:
+        return f.read()
+
+
+# name -> (restype, argtypes) of every symbol include/xview_hip.h declares; its XV_* integers; its structs' members
+SIGNATURES, CONSTANTS, STRUCTS = parse_header(_read_header())
 
 _lib = None
 
@@ -199,7 +101,6 @@ _lib = None
 def source_hash():
     """sha256 (first 16 hex digits) over the library's sources, as csrc/Makefile computes SRC_HASH."""
     import hashlib
-    import re
     mk = open(os.path.join(CSRC, 'Makefile')).read()
     srcs = re.search(r'^SRCS := (.*)$', mk, re.M).group(1).split()
     h = hashlib.sha256()
@@ -250,5 +151,6 @@ def lib():
 
 def check(code, what):
     if code != 0:
-        kind = {-1: 'XV_EINVAL', -2: 'XV_ESHAPE', -3: 'XV_EWORKSPACE'}.get(code, 'hipError_t %d' % code)
+        names = {v: k for k, v in CONSTANTS.items() if k.startswith('XV_E')}
+        kind = names.get(code, 'hipError_t %d' % code)
         raise XvError('%s failed: %s' % (what, kind))

@@ -25,7 +25,8 @@ def _need(t, dtype, name):
         raise TypeError('%s must be a contiguous CUDA tensor of dtype %s' % (name, dtype))
 
 
-BF16, FP8 = 0, 1            # xv_act.dtype (include/xview_hip.h)
+BF16, FP8 = _lib.CONSTANTS['XV_BF16'], _lib.CONSTANTS['XV_FP8']            # xv_act.dtype (include/xview_hip.h)
+XV_ESHAPE = _lib.CONSTANTS['XV_ESHAPE']
 FP8_MAX = 448.0             # largest finite OCP e4m3fn
 
 
@@ -228,7 +229,7 @@ def conv2d_fwd_pair(xa, wa, ba, xb, wb, bb, relu=True, ya=None, yb=None, pa=None
     rc = _lib.lib().xv_conv2d_fwd_pair(xa.xv(), _ptr(wa), _ptr(ba), ctypes.byref(da), pa.xv() if pa is not None else _NULL_ACT,
                                        xb.xv(), _ptr(wb), _ptr(bb), ctypes.byref(db), pb.xv() if pb is not None else _NULL_ACT,
                                        int(bool(relu)), _stream())
-    if rc == -2:
+    if rc == XV_ESHAPE:
         return False
     _lib.check(rc, 'xv_conv2d_fwd_pair')
     if prof is not None:
@@ -276,7 +277,7 @@ def conv_first_pair_fwd(x, w1_hwio, b1, w2_packed, b2, y=None, pooled=None, relu
     rc = _lib.lib().xv_conv_first_pair_fwd(_ptr(x), n, h, w, cin, _ptr(w1_hwio), _ptr(b1), int(bool(relu1)), _ptr(w2_packed),
                                            _ptr(b2), int(bool(relu2)), y.xv() if y is not None else _NULL_ACT,
                                            pooled.xv() if pooled is not None else _NULL_ACT, _stream())
-    if rc == -2:
+    if rc == XV_ESHAPE:
         return False
     _lib.check(rc, 'xv_conv_first_pair_fwd')
     if prof is not None:
@@ -1173,7 +1174,7 @@ def conv2d_fwd_route(x, w_packed, bias, pooled, route):
     _need(route, torch.uint8, 'route')
     with _Profiled('k3', 2.0 * x.n * x.h * x.w * x.c * pooled.c * 9):
         rc = _lib.lib().xv_conv2d_fwd_route(x.xv(), _ptr(w_packed), _ptr(bias), pooled.xv(), _ptr(route), route.numel(), _stream())
-    if rc == -2:
+    if rc == XV_ESHAPE:
         return False
     _lib.check(rc, 'xv_conv2d_fwd_route')
     return True
@@ -1288,7 +1289,7 @@ def conv2d_fwd_stats(x, w_packed, bias, z, st):
         st.conv_rows = torch.empty(rows * 2 * st.c, dtype=torch.float32, device=z.t.device)
     rc = lib.xv_conv2d_fwd_stats(x.xv(), _ptr(w_packed), _ptr(bias), z.xv(), _ptr(st.conv_rows), st.conv_rows.numel() * 4,
                                  _stream())
-    if rc == -2:            # XV_ESHAPE: the generation-4 kernel does not take this shape
+    if rc == XV_ESHAPE:     # the generation-4 kernel does not take this shape
         return False
     _lib.check(rc, 'xv_conv2d_fwd_stats')
     st.conv_rows_n = rows       # bn_forward(have_stats=True) adds the rows up (in the launch that finalises, where it can)
@@ -1471,7 +1472,7 @@ def score_dense_fwd_ups8(low, st, w_score, b_score, num_classes, y, score):
         return False
     rc = _lib.lib().xv_score_dense_fwd_ups8(low.xv(), _ptr(st.scale), _ptr(st.shift), _ptr(w_score), _ptr(b_score), num_classes,
                                             y.xv(), _ptr(score), _stream())
-    if rc == -2:
+    if rc == XV_ESHAPE:
         return False
     _lib.check(rc, 'xv_score_dense_fwd_ups8')
     return True

@@ -1,27 +1,7 @@
 """Grid search over the fusion parameters (experiments/different_evaluation_parameters.py): the host-side flows on hand-written
-expectations, the ABI bookkeeping of the grid-scoring heads and their register budgets (tools/occupancy_scan.py)."""
-import os
-import re
-import shutil
-import sys
-
+expectations, and the capacity query of the grid-scoring head."""
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-
-NEW_ENTRY_POINTS = {'xv_fused_head_grid_score_fwd': 16, 'xv_fused_head_grid_capacity': 1, 'xv_fused_head_joint_hist_fwd': 12}
-
-# (mangled-name fragment, fewest waves per SIMD, most scratch bytes): the budget mc_uncertainty_score_kernel holds
-BUDGETS = [
-    ('fused_head_grid_score_kernelILi12E', 4, 0),
-    ('fused_head_grid_score_kernelILi16E', 4, 0),
-    ('fused_head_grid_score_kernelILi', 1, 0),
-    ('fused_head_joint_hist_kernelILi12E', 4, 0),
-    ('fused_head_joint_hist_kernelILi16E', 4, 0),
-    ('fused_head_joint_hist_kernelILi', 1, 0),
-]
 
 
 def test_parameter_combinations_order_and_copies():
@@ -96,23 +76,6 @@ def test_bayes_host_decision_and_confusion_from_joint_hist():
     assert np.array_equal(cm, ref) and cm.sum() == hist.sum()
 
 
-def test_new_entry_points_are_declared_listed_and_defined():
-    from modular_semantic_segmentation_amd import _lib
-    header = open(os.path.join(ROOT, 'include', 'xview_hip.h')).read()
-    csrc = os.path.join(ROOT, 'modular_semantic_segmentation_amd', 'csrc')
-    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith('.hip')}
-    for name, nargs in NEW_ENTRY_POINTS.items():
-        decl = re.search(r'\bint %s\(([^;{]*)\);' % name, header)
-        assert decl, '%s is not declared in include/xview_hip.h' % name
-        assert len(decl.group(1).split(',')) == nargs, name
-        assert name in _lib.SIGNATURES, '%s is not in _lib.SIGNATURES' % name
-        assert len(_lib.SIGNATURES[name][1]) == nargs, name
-        defn = re.search(r'extern "C" int %s\(([^{;]*)\)\s*\{' % name, sources['heads.hip'])
-        assert defn, '%s is not defined in csrc/heads.hip' % name
-        assert len(defn.group(1).split(',')) == nargs, name
-    assert re.search(r'xv_version\(void\)\s*\{\s*return 604;', ''.join(sources.values()))
-
-
 def test_grid_capacity():
     """No GPU call: the capacity is LDS arithmetic on the host."""
     from modular_semantic_segmentation_amd import _lib
@@ -121,21 +84,3 @@ def test_grid_capacity():
     assert lib.xv_fused_head_grid_capacity(12) >= 16 and lib.xv_fused_head_grid_capacity(32) >= 1
     assert all(a >= b for a, b in zip(cap, cap[1:])), cap
     assert lib.xv_fused_head_grid_capacity(1) == 0 and lib.xv_fused_head_grid_capacity(33) == 0
-
-
-@pytest.mark.skipif(shutil.which('hipcc') is None, reason='hipcc not on PATH')
-def test_register_budgets_of_the_grid_scoring_kernels():
-    import occupancy_scan
-    table = occupancy_scan.scan([os.path.join(occupancy_scan.CSRC, 'heads.hip')], workers=1)
-    for frag, min_waves, max_scratch in BUDGETS:
-        rows = [r for r in table['heads.hip'] if frag in r[0]]
-        assert rows, 'no kernel matching %s in heads.hip' % frag
-        for kern, regs, scratch, waves in rows:
-            assert waves >= min_waves and scratch <= max_scratch, \
-                '%s: %d waves per SIMD (%d registers), %d B scratch; budget: >= %d waves, <= %d B' % (
-                    kern, waves, regs, scratch, min_waves, max_scratch)
-
-    def instantiations(frag):
-        return sorted(int(re.search(r'ILi(\d+)E', r[0]).group(1)) for r in table['heads.hip'] if frag in r[0])
-    assert instantiations('fused_head_grid_score_kernelILi') == instantiations('fused_head_joint_hist_kernelILi') == \
-        [4, 8, 12, 16, 20, 24, 28, 32]

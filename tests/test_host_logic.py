@@ -1,5 +1,6 @@
 """CPU-only tests: host logic of the product against the reference-generated golden vectors,
 and the C-ABI library's exports (no compute calls without a GPU)."""
+import ctypes
 import json
 import os
 import re
@@ -7,6 +8,7 @@ import re
 import numpy as np
 import pytest
 import torch
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 from modular_semantic_segmentation_amd import _lib, get_model
 from modular_semantic_segmentation_amd import base_model, bayes_mix, custom_layers, dirichlet_fit, dirichlet_mix, fcn
@@ -35,6 +37,125 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert handle.xv_packed_weight_bytes_f8(1, 64, 64) == 0                         # 1x1: 128-channel chunks
     assert handle.xv_packed_weight_bytes(1, 64, 128) == 64 * 128 * 2
     assert handle.xv_packed_weight_bytes(3, 3, 64) == 0          # first layer is not an MFMA conv
+
+
+# Hand-written from the header, independent of the parser: one entry per rule of its type map
+_ACT = POINTER(_lib.xv_act)
+PINNED_SIGNATURES = {
+    'xv_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
+                             c_void_p]),
+    'xv_dropout_samples': (c_int, [_ACT, _ACT, c_int, c_float, c_uint64, c_uint64, c_void_p]),
+    'xv_bayes_fuse': (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    'xv_variance_fuse': (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    'xv_conv2d_fwd_ws': (c_int, [_ACT, c_void_p, c_void_p, _ACT, _ACT, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'xv_source_hash': (c_char_p, []),
+    'xv_packed_weight_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'xv_uncertainty_dirichlet_head_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+}
+# the source file that has to hold the definition, for the entry points whose feature pinned it
+DEFINED_IN = {'xv_uncertainty_stats': 'fusion.hip', 'xv_mc_uncertainty_score_fwd': 'heads.hip',
+              'xv_fused_head_grid_score_fwd': 'heads.hip', 'xv_fused_head_grid_capacity': 'heads.hip',
+              'xv_fused_head_joint_hist_fwd': 'heads.hip'}
+OPS_WRAPPERS = ('dropout_pixels', 'dropout_pixels_samples', 'uncertainty_moments', 'uncertainty_dirichlet_head',
+                'uncertainty_dirichlet_fuse', 'uncertainty_weights')
+
+
+def _count(params):
+    return 0 if params.strip() in ('', 'void') else len(params.split(','))
+
+
+def test_abi_is_one_table_header_sources_and_ctypes():
+    """Every symbol of include/xview_hip.h: in _lib.SIGNATURES (which is derived from the header), defined once in csrc/ with
+    the declared number of parameters; the two ctypes structures against the header's members; the parser against
+    hand-written expectations."""
+    header = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', open(os.path.join(ROOT, 'include', 'xview_hip.h')).read(), flags=re.S)
+    declared = {name: _count(params) for name, params in re.findall(r'\b(xv_\w+)\s*\(([^()]*)\)\s*;', header)}
+    assert len(declared) >= 154 and set(declared) == set(_lib.SIGNATURES), set(declared) ^ set(_lib.SIGNATURES)
+
+    csrc = os.path.join(ROOT, 'modular_semantic_segmentation_amd', 'csrc')
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith('.hip')}
+    # Every source file reaches the header through xv_common.h, so the compiler itself refuses a definition whose types conflict
+    # with its declaration (both are extern "C": same name, other parameters = "conflicting types"); what is left to check here
+    # is that each declaration HAS a definition, once, and the parameter counts as a second line of defence.
+    assert '#include "../../include/xview_hip.h"' in open(os.path.join(csrc, 'xv_common.h')).read()
+    for fname, text in sources.items():
+        assert '#include "xv_common.h"' in text, fname
+    defined = {}
+    for fname, text in sources.items():
+        for name, params in re.findall(r'extern "C"\s+(?:const\s+)?\w+\s*\*?\s*(xv_\w+)\s*\(([^{;]*)\)\s*\{', text):
+            defined.setdefault(name, []).append((fname, _count(params)))
+    for name, nargs in declared.items():
+        assert len(defined.get(name, [])) == 1, '%s: defined in %s' % (name, defined.get(name))
+        fname, ndef = defined[name][0]
+        assert ndef == nargs == len(_lib.SIGNATURES[name][1]), (name, ndef, nargs, len(_lib.SIGNATURES[name][1]))
+        assert DEFINED_IN.get(name, fname) == fname, name
+    assert len(re.findall(r'xv_version\(void\)\s*\{\s*return 604;', ''.join(sources.values()))) == 1
+    # the plain uncertainty head and its entry point take no temperature (the scoring head does)
+    assert 'inv_t' not in re.search(r'void mc_uncertainty_head_kernel\((.*?)\)\s*\{', sources['heads.hip'], re.S).group(1)
+    from modular_semantic_segmentation_amd import ops
+    for name in OPS_WRAPPERS:
+        assert callable(getattr(ops, name)), name
+
+    for name, expected in PINNED_SIGNATURES.items():
+        assert _lib.SIGNATURES[name] == expected, name
+    assert _lib.CONSTANTS == {'XV_OK': 0, 'XV_EINVAL': -1, 'XV_ESHAPE': -2, 'XV_EWORKSPACE': -3, 'XV_BF16': 0, 'XV_FP8': 1}
+    assert (ops.BF16, ops.FP8, ops.XV_ESHAPE) == (0, 1, -2)
+
+    # the hand-written structures: the header's members in order, by name, type and width
+    assert sorted(_lib.STRUCTS) == ['xv_act', 'xv_pack_desc']
+    for cls, size in ((_lib.xv_act, 32), (_lib.xv_pack_desc, 40)):
+        members = _lib.STRUCTS[cls.__name__]
+        assert [n for n, _ in cls._fields_] == [n for n, _ in members], cls.__name__
+        for (field, ctype), (_, ctext) in zip(cls._fields_, members):
+            want = c_void_p if ctext.endswith('*') else {'int32_t': c_int32}[ctext]
+            assert ctype is want and ctypes.sizeof(ctype) == (8 if want is c_void_p else 4), (cls.__name__, field, ctext)
+        assert ctypes.sizeof(cls) == size
+    assert _lib.STRUCTS['xv_act'][0] == ('data', 'void*') and _lib.STRUCTS['xv_pack_desc'][0] == ('w_hwio', 'const float*')
+
+
+def test_header_parser_on_synthetic_headers():
+    for bad in ('int xv_f(double x, void* stream);', 'void xv_f(int n);', 'int xv_f(unsigned n);', 'int xv_f(float*** p);',
+                'int xv_f(int);', 'int xv_f(int n); int xv_f(int n);', 'struct s;'):
+        with pytest.raises(_lib.XvError, match='xview_hip.h'):
+            _lib.parse_header(bad)
+    with pytest.raises(_lib.XvError, match='xv_bad_one'):          # the message names the declaration
+        _lib.parse_header('int xv_good(int n);\nint xv_bad_one(int n, long m);')
+    text = '''
+        #define XV_SEVEN (-7)     /* a code */
+        #define XV_THREE 3        // another
+        typedef struct xv_thing {
+          const float* p;         /* a pointer */
+          int32_t a, b;
+        } xv_thing;
+        /* int xv_commented_out(int n); */
+        // int xv_commented_out_too(int n);
+        int xv_multi(const float* a,   /* first */
+                     int64_t n,        // count
+                     const float* const* table,
+                     /* a line of its own, with a ; and a , in it */
+                     size_t bytes, float rate, uint64_t seed, const xv_act* y,
+                     const xv_pack_desc* descs,
+                     void* stream);
+        size_t xv_none(void);
+        const char* xv_name(void);
+    '''
+    functions, constants, structs = _lib.parse_header(text)
+    assert functions == {
+        'xv_multi': (c_int, [c_void_p, c_int64, POINTER(c_void_p), c_size_t, c_float, c_uint64, POINTER(_lib.xv_act), c_void_p,
+                             c_void_p]),
+        'xv_none': (c_size_t, []),
+        'xv_name': (c_char_p, []),
+    }
+    assert constants == {'XV_SEVEN': -7, 'XV_THREE': 3}
+    assert structs == {'xv_thing': [('p', 'const float*'), ('a', 'int32_t'), ('b', 'int32_t')]}
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, 'HEADER', str(tmp_path / 'nope.h'))
+    with pytest.raises(_lib.XvError, match='nope.h'):
+        _lib._read_header()
 
 
 def test_abi_rejects_bad_arguments_without_touching_the_gpu():

@@ -1,20 +1,11 @@
 """Uncertainty benchmarks without a GPU (uncertainty_model.py): the bit-pattern histogram bins, the ROC from two histogram rows
-against the exact rank statistic, the ABI bookkeeping and register budgets of the two new kernels (as
-test_uncertainty_registers_cpu.py), and the model's host logic.
+against the exact rank statistic, and the model's host logic.
 
 The tie bound: binning is monotone in the value, so a (positive, negative) pair whose members fall into different bins is
 ordered by the bins as by the values; only pairs that share a bin can differ, each by at most one half of 1 / (P N) (the
 histogram gives it one half; the truth is 0, one half or 1): |auroc_binned - auroc_exact| <= 0.5 sum_b pos_b neg_b / (P N)."""
-import os
-import re
-import shutil
-import sys
-
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 from modular_semantic_segmentation_amd import uncertainty_model as um
 
@@ -114,59 +105,6 @@ def test_binned_auroc_is_within_the_tie_bound_of_the_rank_statistic(seed, m, o):
     print('seed %d M=%d octaves=%d: binned %.6f exact %.6f |diff| %.3g bound %.3g' % (seed, m, o, auroc, exact, abs(auroc - exact), bound))
     assert 0.55 < exact < 0.999 and 0 < bound < 0.25              # the inputs are neither separable nor noise
     assert abs(auroc - exact) <= bound + 1e-12                      # (1e-12: the float64 rounding of the rank sum)
-
-
-# ---- ABI bookkeeping and register budgets -------------------------------------------------------------------------------------
-
-NEW_ENTRY_POINTS = {'xv_uncertainty_stats': 13, 'xv_mc_uncertainty_score_fwd': 16}
-
-# (file, mangled-name fragment, fewest waves per SIMD, most scratch bytes): the scoring head holds mc_uncertainty_head_kernel's
-# budget (tests/test_uncertainty_registers_cpu.py)
-BUDGETS = [
-    ('heads.hip', 'mc_uncertainty_score_kernelILi12E', 4, 0),
-    ('heads.hip', 'mc_uncertainty_score_kernelILi16E', 4, 0),
-    ('heads.hip', 'mc_uncertainty_score_kernelILi', 1, 0),
-    ('fusion.hip', 'uncertainty_stats_kernel', 4, 0),
-]
-
-
-def test_new_entry_points_are_declared_listed_and_defined():
-    from modular_semantic_segmentation_amd import _lib
-    header = open(os.path.join(ROOT, 'include', 'xview_hip.h')).read()
-    csrc = os.path.join(ROOT, 'modular_semantic_segmentation_amd', 'csrc')
-    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith('.hip')}
-    home = {'xv_uncertainty_stats': 'fusion.hip', 'xv_mc_uncertainty_score_fwd': 'heads.hip'}
-    for name, nargs in NEW_ENTRY_POINTS.items():
-        decl = re.search(r'\bint %s\(([^;{]*)\);' % name, header)
-        assert decl, '%s is not declared in include/xview_hip.h' % name
-        assert len(decl.group(1).split(',')) == nargs, name
-        assert name in _lib.SIGNATURES, '%s is not in _lib.SIGNATURES' % name
-        assert len(_lib.SIGNATURES[name][1]) == nargs, name
-        defn = re.search(r'extern "C" int %s\(([^{;]*)\)\s*\{' % name, sources[home[name]])
-        assert defn, '%s is not defined in csrc/%s' % (name, home[name])
-        assert len(defn.group(1).split(',')) == nargs, name
-    assert re.search(r'xv_version\(void\)\s*\{\s*return 604;', ''.join(sources.values()))
-    # the existing head and its entry point take no temperature
-    assert 'inv_t' not in re.search(r'void mc_uncertainty_head_kernel\((.*?)\)\s*\{', sources['heads.hip'], re.S).group(1)
-
-
-@pytest.mark.skipif(shutil.which('hipcc') is None, reason='hipcc not on PATH')
-def test_register_budgets_of_the_scoring_kernels():
-    import occupancy_scan
-    csrc = occupancy_scan.CSRC
-    table = occupancy_scan.scan([os.path.join(csrc, f) for f in ('fusion.hip', 'heads.hip')], workers=2)
-    for fname, frag, min_waves, max_scratch in BUDGETS:
-        rows = [r for r in table[fname] if frag in r[0]]
-        assert rows, 'no kernel matching %s in %s' % (frag, fname)
-        for kern, regs, scratch, waves in rows:
-            assert waves >= min_waves and scratch <= max_scratch, \
-                '%s: %d waves per SIMD (%d registers), %d B scratch; budget: >= %d waves, <= %d B' % (
-                    kern, waves, regs, scratch, min_waves, max_scratch)
-
-    def instantiations(frag):
-        return sorted(int(re.search(r'ILi(\d+)E', r[0]).group(1)) for r in table['heads.hip'] if frag in r[0])
-    assert instantiations('mc_uncertainty_score_kernelILi') == instantiations('mc_uncertainty_head_kernelILi') == \
-        [4, 8, 12, 16, 20, 24, 28, 32]
 
 
 # ---- model host logic ---------------------------------------------------------------------------------------------------------
