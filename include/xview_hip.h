@@ -23,6 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "xview_augment.h"   /* xv_augment_plan, the record of xv_augment_batch */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -805,6 +807,34 @@ int xv_score_lowres_f32(const float* fused, int n, int h, int w, int u, const fl
                         void* stream);
 int xv_decoder_head_from_scores(const float* S, const float* b_score, int n, int hi, int wi, int num_classes, float* score,
                                 float* prob, int64_t* label, void* stream);
+
+/* ---- on-device training augmentation (csrc/augment.hip; datasets/device_augmentation.py) ---------------------------------
+ * The host chain of datasets/augmentation.py -- scale, rotate + centre crop, shear, crop, flips, contrast / brightness / gamma,
+ * label flip / merge -- then crop_multiple and the float cast of DataBaseclass._load_sample, for a batch of N output images in
+ * ONE launch, bit for bit what the host computes (float64 in numpy's operation order, no contraction, rint = half to even).
+ *   rgb uint8 [M][H][W][3], depth uint16 [M][H][W], labels int32 [M][H][W]   a resident pool of equally sized sources
+ *   index int32 [N]       source image of each output image (no gathered copy is made); index_host: the same N values in
+ *                         host memory, checked against [0, M) before the launch
+ *   plans [N]             one xv_augment_plan record (include/xview_augment.h, xv_augment_plan_bytes() bytes each) per output
+ *                         image in device memory; plans_host: the same N records in host memory, checked before the launch
+ *   luts uint8 [N][256]   per output image the composed contrast -> brightness -> gamma map (identity: 0..255), made on the
+ *                         host by the host's own formulas; the kernel only indexes it with the augmented rgb value
+ *   out_rgb float32 [N][S][S][3], out_depth float32 [N][S][S][1], out_labels int32 [N][S][S]: what the trainers take
+ * S = the crop size cut down to a multiple of 16.  An output pixel is mapped back through flips and crop to a pixel of the
+ * sheared image; that is a bilinear blend (zero outside, rounded to the source integer type) of four pixels of the rotated and
+ * centre-cropped image; each of those a blend of four canvas taps of the scaled image; each of those a rounded bilinear blend
+ * of four source pixels (rgb) or a floor-index nearest pick (depth, labels).  Rotation and shear resample labels bilinearly
+ * too, as the host chain does.  A stage the plan leaves out is skipped.  Nothing intermediate is written to memory.
+ * XV_EINVAL, with no launch: a null pointer; M, H, W or N not positive (N at most 65535); S not a positive multiple of 16; an
+ * index_host entry outside [0, M); a plans_host record with unknown stage bits, a non-finite matrix, a stage size that
+ * contradicts the stages before it, a centre-crop window that leaves its canvas, or a crop window that is smaller than S or
+ * leaves its stage's image.  The two host copies must hold what the device buffers hold: the kernel clamps every source read
+ * into the selected image, but computes from the device copies.                                                            */
+size_t xv_augment_plan_bytes(void);
+int xv_augment_batch(const uint8_t* rgb, const uint16_t* depth, const int32_t* labels, int M, int H, int W,
+                     const int32_t* index, const int32_t* index_host, const xv_augment_plan* plans,
+                     const xv_augment_plan* plans_host, const uint8_t* luts, int N, int S, float* out_rgb, float* out_depth,
+                     int32_t* out_labels, void* stream);
 
 #ifdef __cplusplus
 }

@@ -104,7 +104,8 @@ def source_hash():
     mk = open(os.path.join(CSRC, 'Makefile')).read()
     srcs = re.search(r'^SRCS := (.*)$', mk, re.M).group(1).split()
     h = hashlib.sha256()
-    for rel in srcs + ['xv_common.h', '../../include/xview_hip.h', 'Makefile']:
+    hdrs = re.search(r'^HDRS := (.*)$', mk, re.M).group(1).split()
+    for rel in srcs + hdrs + ['Makefile']:
         with open(os.path.join(CSRC, rel), 'rb') as f:
             h.update(f.read())
     return h.hexdigest()[:16]

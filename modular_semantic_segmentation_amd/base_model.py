@@ -252,7 +252,12 @@ class BaseModel(object):
         if output:
             print('INFO: Start training')
         # the next batches are staged into pinned memory and uploaded while the current step runs (host_pipeline.py)
-        batches = iter(self._device_batches(endless(), labels=True))
+        if hasattr(dataset, 'training_batches'):
+            # a dataset that makes its own training batches on the device (datasets/device_augmentation.py DeviceTrainset):
+            # already resident, nothing to stage
+            batches = iter(dataset.training_batches(self.config['batchsize']))
+        else:
+            batches = iter(self._device_batches(endless(), labels=True))
         for i in range(iterations):
             loss = self._train_batch(next(batches))
             self.global_step += 1

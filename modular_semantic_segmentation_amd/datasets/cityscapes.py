@@ -116,15 +116,17 @@ class Cityscapes(DataBaseclass):
         blob['depth'] = blob['depth'][:, :, None]
         return blob
 
-    def _get_data(self, image_path, training_format=False):
+    def _get_raw_blob(self, image_path):
         if self.in_memory:
             if image_path not in self.images:
                 self.images[image_path] = self._load_data(image_path)
-            blob = {m: v.copy() for m, v in self.images[image_path].items()}
-        else:
-            blob = self._load_data(image_path)
+            return {m: v.copy() for m, v in self.images[image_path].items()}
+        return self._load_data(image_path)
+
+    def _get_data(self, image_path, training_format=False):
+        blob = self._get_raw_blob(image_path)
         if training_format:
-            blob = augmentate(blob, **self.config['augmentation'])
+            blob = augmentate(blob, **self._augmentation_arguments())
         return blob
 
     def get_ego_vehicle_mask(self, image_path):

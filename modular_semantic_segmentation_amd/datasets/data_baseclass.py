@@ -66,6 +66,14 @@ class DataBaseclass:
     def _get_data(self, **kwargs):
         raise NotImplementedError
 
+    def _get_raw_blob(self, **item):
+        """The item's decoded images as `_get_data` hands them to the augmentation: raw dtypes, nothing drawn."""
+        raise NotImplementedError
+
+    def _augmentation_arguments(self):
+        """The keyword arguments `_get_data` augments with in training format."""
+        return dict(self.config['augmentation'])
+
     def _load_sample(self, item, training_format):
         if self.print_info:
             print(item)
@@ -89,6 +97,17 @@ class DataBaseclass:
     # `tf_dataset` keeps the reference's keyword: True = lazily loaded stream, False = numpy batch.
     def get_trainset(self, tf_dataset=True, training_format=True):
         return self._serve(self.trainset, tf_dataset, training_format=training_format)
+
+    def get_device_trainset(self, device='cuda', num_items=None):
+        """The train items as a `DeviceTrainset`: loaded once without augmentation and kept resident as raw integer images
+        (rgb uint8, depth uint16, labels int32 -- the host chain's rounding and clipping give the same values on these as on a
+        narrower integer type, every resampled value being a convex blend of stored ones); `BaseModel.fit` then draws and
+        augments every batch on the device, with the draws and in the order of `get_trainset()`'s stream."""
+        from .device_augmentation import DeviceTrainset
+        blobs = [self._get_raw_blob(**item) for item in self.trainset[:num_items]]
+        pool = {m: [np.asarray(blob[m]).astype(DeviceTrainset._dtypes[m], casting='same_kind') for blob in blobs]
+                for m in DeviceTrainset.modalities}
+        return DeviceTrainset(pool, self._augmentation_arguments(), device)
 
     def get_testset(self, num_items=None, tf_dataset=True):
         return self._serve(self.testset[:num_items], tf_dataset)

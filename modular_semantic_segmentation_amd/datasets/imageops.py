@@ -72,11 +72,15 @@ def scale_image(image, factor, nearest):
     return (resize_nearest if nearest else resize_linear)(image, out_h, out_w)
 
 
+def invert_affine(matrix):
+    """[3,3] float64 inverse of a [2,3] source -> destination matrix: the destination -> source map `warp_affine` samples by."""
+    return np.linalg.inv(np.vstack([np.asarray(matrix, dtype=np.float64), [0.0, 0.0, 1.0]]))
+
+
 def warp_affine(image, matrix, out_w, out_h):
     """`cv2.warpAffine(image, matrix, (out_w, out_h), flags=INTER_LINEAR)`: `matrix` [2,3] maps source
     to destination coordinates (x, y); pixels that fall outside the source read 0."""
-    full = np.vstack([np.asarray(matrix, dtype=np.float64), [0.0, 0.0, 1.0]])
-    inv = np.linalg.inv(full)
+    inv = invert_affine(matrix)
     ys, xs = np.mgrid[0:out_h, 0:out_w].astype(np.float64)
     sx = inv[0, 0] * xs + inv[0, 1] * ys + inv[0, 2]
     sy = inv[1, 0] * xs + inv[1, 1] * ys + inv[1, 2]

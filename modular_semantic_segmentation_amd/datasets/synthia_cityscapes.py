@@ -122,11 +122,17 @@ class SynthiaCityscapes(DataBaseclass):
                 blob[m] = imageops.resize_nearest(blob[m], 384, 768)
         return blob
 
-    def _get_data(self, image_name=False, image=False, training_format=True):
+    def _get_raw_blob(self, image_name=False, image=False):
         assert image_name or image, 'an item names a file or carries a decoded image'
-        blob = self._load_data(image_name) if image_name else {m: v.copy() for m, v in image.items()}
+        return self._load_data(image_name) if image_name else {m: v.copy() for m, v in image.items()}
+
+    def _augmentation_arguments(self):
+        return {k: self.config['augmentation'][k] for k in (
+            'scale', 'crop', 'hflip', 'vflip', 'gamma', 'contrast', 'brightness', 'rotate', 'shear')}
+
+    def _get_data(self, image_name=False, image=False, training_format=True):
+        blob = self._get_raw_blob(image_name=image_name, image=image)
         if training_format:
-            blob = augmentate(blob, **{k: self.config['augmentation'][k] for k in (
-                'scale', 'crop', 'hflip', 'vflip', 'gamma', 'contrast', 'brightness', 'rotate', 'shear')})
-        blob['depth'] = blob['depth'][:, :, None]
+            blob = augmentate(blob, **self._augmentation_arguments())
+        blob['depth'] = blob['depth'][:, :, None]         # (after augmenting, as the reference's reader)
         return blob

@@ -1521,3 +1521,57 @@ def score_dense_bwd(u, dscore, w_score, num_classes, dw_score, db_score, du):
                                    _ptr(ws), ws.numel() * 4, _stream())
     _lib.check(rc, 'xv_score_dense_bwd_ws')
     return du
+
+
+# ---- on-device training augmentation (csrc/augment.hip) ----------------------------------------------------------------------
+
+def augment_plan_bytes():
+    return int(_lib.lib().xv_augment_plan_bytes())
+
+
+def augment_batch(pool, index, plans, luts):
+    """The host augmentation chain for a batch in one launch (include/xview_hip.h xv_augment_batch).
+
+    pool    {'rgb': uint8 [M,H,W,3], 'depth': uint16 [M,H,W] or [M,H,W,1], 'labels': int32 [M,H,W]} resident tensors
+    index   host int32 [N]: the source image of each output image
+    plans   host numpy record array [N] of xv_augment_plan (datasets/device_augmentation.py pack_plans)
+    luts    host uint8 [N,256]: the composed photometric table of each output image
+    Index, plans and tables travel to the device in ONE copy; the call checks its host copies of them and refuses
+    (XvError: XV_EINVAL) before anything is launched.  Returns rgb float32 [N,S,S,3], depth float32 [N,S,S,1], labels int32
+    [N,S,S] with S the plans' crop size cut down to a multiple of 16."""
+    import numpy as np
+    rgb, depth, labels = pool['rgb'], pool['depth'], pool['labels']
+    _need(rgb, torch.uint8, "pool['rgb']")
+    _need(depth, torch.uint16, "pool['depth']")
+    _need(labels, torch.int32, "pool['labels']")
+    M, H, W = rgb.shape[:3]
+    if tuple(rgb.shape) != (M, H, W, 3) or tuple(depth.shape) not in ((M, H, W), (M, H, W, 1)) or \
+            tuple(labels.shape) != (M, H, W):
+        raise ValueError('pool shapes %s / %s / %s are not [M,H,W,3] / [M,H,W(,1)] / [M,H,W] of one size' % (
+            tuple(rgb.shape), tuple(depth.shape), tuple(labels.shape)))
+    index = np.ascontiguousarray(index, dtype=np.int32)
+    plans = np.ascontiguousarray(plans)
+    luts = np.ascontiguousarray(luts, dtype=np.uint8)
+    N = len(index)
+    if plans.dtype.itemsize != augment_plan_bytes():
+        raise ValueError('plan records of %d bytes, the library takes %d' % (plans.dtype.itemsize, augment_plan_bytes()))
+    if N < 1 or plans.shape != (N,) or luts.shape != (N, 256):
+        raise ValueError('index [N], plans [N] and luts [N,256] must agree (N >= 1)')
+    sizes = set(int(s) for s in plans['crop_size'])
+    if len(sizes) != 1:
+        raise ValueError('the plans of one batch crop to different sizes: %s' % sorted(sizes))
+    S = sizes.pop() // 16 * 16
+    # one host buffer, one upload: records (8-byte aligned at the front), then the indices, then the tables
+    host = np.concatenate([plans.view(np.uint8).reshape(-1), index.view(np.uint8), luts.reshape(-1)])
+    dev = torch.from_numpy(host).to(rgb.device)
+    nplan, nidx = plans.nbytes, index.nbytes
+    out_rgb = torch.empty((N, max(S, 0), max(S, 0), 3), dtype=torch.float32, device=rgb.device)
+    out_depth = torch.empty((N, max(S, 0), max(S, 0), 1), dtype=torch.float32, device=rgb.device)
+    out_labels = torch.empty((N, max(S, 0), max(S, 0)), dtype=torch.int32, device=rgb.device)
+    base = dev.data_ptr()
+    rc = _lib.lib().xv_augment_batch(_ptr(rgb), _ptr(depth), _ptr(labels), M, H, W, ctypes.c_void_p(base + nplan),
+                                     index.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(base),
+                                     plans.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(base + nplan + nidx), N, S,
+                                     _ptr(out_rgb), _ptr(out_depth), _ptr(out_labels), _stream())
+    _lib.check(rc, 'xv_augment_batch')
+    return out_rgb, out_depth, out_labels

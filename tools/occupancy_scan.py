@@ -16,7 +16,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'modular_semantic_segmentation_amd', 'csrc')
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-S', '--cuda-device-only']
-EXTRA = {'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}     # as the Makefile builds it
+EXTRA = {'conv_first.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'augment.hip': ['-ffp-contract=off']}     # as the Makefile builds them
 
 
 def scan_file(path, digest=False):
