@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void im2col_pair_kernel(const u32x4* __restric
 // channel group), so a workgroup walks 1024 consecutive 16-byte elements of one row and only has to split the in-row index
 // into (x, tap, channel group).  The flat forms do that with three 64-bit divisions per 16 bytes -- a few hundred
 // instructions per element, which made a pure copy ALU-bound at 2.7 TB/s of writes; here the two divisions are one
-// v_mul_hi each by a reciprocal the launcher computed (exact while row_length * divisor < 2^32, which it checks).
+// v_mul_hi each by a reciprocal the launcher computed (exact while row_length * divisor < 2^32 and divisor >= 2, which it
+// checks: rows_form_ok).
 __device__ __forceinline__ uint32_t div_magic(uint32_t n, uint32_t magic) { return __umulhi(n, magic); }
 
 __global__ __launch_bounds__(256) void im2col_pair_rows_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ z, int H,
@@ -144,11 +145,13 @@ __global__ __launch_bounds__(256) void gather_conv7s2_rows_kernel(const u32x4* _
   }
 }
 
-// floor(2^32 / d) + 1: __umulhi(n, magic) == n / d for every n with n * d < 2^32
+// floor(2^32 / d) + 1 for d >= 2: __umulhi(n, magic) == n / d for every n with n * d < 2^32.  NOT for d = 1: 2^32 / 1 does
+// not fit 32 bits, the magic wraps to 1 and every quotient comes out 0 -- rows_form_ok refuses that divisor.
 inline uint32_t magic_of(uint32_t d) { return (uint32_t)((((uint64_t)1) << 32) / d) + 1u; }
-inline bool rows_form_ok(int64_t rows, int64_t row_len, int64_t g8) {
+// g8, c8: the two divisors of the row kernels.  c8 = 1 (C = 8) has no reciprocal (magic_of) and takes the flat kernels.
+inline bool rows_form_ok(int64_t rows, int64_t row_len, int64_t g8, int64_t c8) {
   static const bool flat = getenv("XV_GATHER_FLAT") != nullptr && atoi(getenv("XV_GATHER_FLAT")) != 0;  // A/B switch
-  return rows <= 65535 && row_len * g8 < (((int64_t)1) << 32) && !flat;
+  return rows <= 65535 && c8 >= 2 && row_len * g8 < (((int64_t)1) << 32) && !flat;
 }
 
 // ---- transposes of the three gathers (training) and the residual add, all written as gathers themselves: every
@@ -416,7 +419,7 @@ extern "C" int xv_gather_conv7s2(const xv_act* x, const xv_act* z, void* stream)
                  z->h > 0);
   const int64_t total = (int64_t)z->n * z->h * z->w * (z->c >> 3);
   const int c8 = x->c >> 3, g8 = 9 * c8;
-  if (rows_form_ok((int64_t)z->n * z->h, (int64_t)z->w * g8, g8)) {
+  if (rows_form_ok((int64_t)z->n * z->h, (int64_t)z->w * g8, g8, c8)) {
     hipLaunchKernelGGL(gather_conv7s2_rows_kernel, dim3((z->w * g8 + 1023) / 1024, z->n * z->h), dim3(256), 0,
                        (hipStream_t)stream, (const u32x4*)x->data, (u32x4*)z->data, z->h, z->w, c8, magic_of(g8),
                        magic_of(c8));
@@ -434,7 +437,7 @@ extern "C" int xv_im2col_dilated_pair(const xv_act* x, int dilation1, int dilati
                  dilation1 >= 1 && dilation2 >= 1);
   const int64_t total = (int64_t)z->n * z->h * z->w * (z->c >> 3);
   const int c8 = x->c >> 3, g8 = 18 * c8;
-  if (rows_form_ok((int64_t)z->n * z->h, (int64_t)z->w * g8, g8)) {
+  if (rows_form_ok((int64_t)z->n * z->h, (int64_t)z->w * g8, g8, c8)) {
     hipLaunchKernelGGL(im2col_pair_rows_kernel, dim3((z->w * g8 + 1023) / 1024, z->n * z->h), dim3(256), 0,
                        (hipStream_t)stream, (const u32x4*)x->data, (u32x4*)z->data, z->h, z->w, c8, magic_of(g8),
                        magic_of(c8), dilation1, dilation2);
