@@ -21,8 +21,6 @@ gathers (csrc/resnet_ops.hip) that express the rest through them:
 Training: adapnet_trainer.AdapnetTrainer (every batch norm in training mode, the gathers' transposes, both deconv
 kernels trained as the reference trains them).
 """
-import os
-
 import numpy as np
 import torch
 
@@ -154,8 +152,6 @@ class AdapnetEngine(object):
         self.device = torch.device(device)
         self.Up = ((self.U + 63) // 64) * 64
         self._arena = {}
-        self.implicit_pairs = os.environ.get('XV_IMPLICIT_PAIRS', '1') != '0'   # 0: the materialised form everywhere (A/B)
-        self.fused_first = os.environ.get('XV_ADAPNET_FUSED_FIRST', '1') != '0'  # 0: block_0_1's map written, then gathered
         self.load(variables)
 
     # ---- weights -------------------------------------------------------------------------------------------
@@ -269,7 +265,7 @@ class AdapnetEngine(object):
             raise ValueError('H and W must be multiples of 16 (augmentation.py:244-262 crop_multiple)')
         L = {}
         z = self._act('block_0_2/operand', n, h // 2, w // 2, 9 * 64)
-        if not keep_all and self.fused_first and cin in (1, 3):
+        if not keep_all and cin in (1, 3):
             # block_0_1 straight into the operand of block_0_2: its 64-channel full-resolution map is neither written nor read
             ops.conv2d_first_gather7s2_fwd(x.contiguous(), self.w['block_0_1'], self.b['block_0_1'], z, relu=True)
         else:
@@ -291,7 +287,7 @@ class AdapnetEngine(object):
             else:
                 f1, f2, cout, d1, d2, shortcut_conv = args
                 s1 = self._conv(name + '/stage_1', inp, 1, f1)
-                if self.implicit_pairs and ops.dilated_pair_implicit_ok(f1, f2):
+                if ops.dilated_pair_implicit_ok(f1, f2):
                     # the nine taps of each half gathered by the GEMM's own loads: no 18 f1 operand (ops.conv_dilated_pair)
                     s2 = ops.conv_dilated_pair(s1, self.w[name + '/stage_2'], self.b[name + '/stage_2'], d1, d2, relu=True,
                                                y=self._act(name + '/stage_2', s1.n, s1.h, s1.w, f2))

@@ -20,8 +20,6 @@ through the inverse index map (every kernel element sits at exactly one derived 
 conv's data gradient.  `first_deconvolution_conv` is therefore trained on all of its output channels.  The loss is the
 reference's: the mean cross-entropy over the labelled pixels divided once more by their number (adapnet.py:202-203).
 """
-import os
-
 import numpy as np
 import torch
 
@@ -30,8 +28,7 @@ from .adapnet import _conv_scopes, conv7s2_as_3x3
 from .custom_layers import dense_deconv_as_conv3x3
 from .trainer import FcnTrainer
 
-_IMPLICIT_PAIRS = os.environ.get('XV_IMPLICIT_PAIRS', '1') != '0'   # 0: the atrous pairs through the im2col operand (A/B)
-_FUSE_ACCUM = os.environ.get('XV_ADAPNET_FUSE_ACCUM', '1') != '0'   # 0: every second gradient of a tensor through an add pass (A/B)
+_IMPLICIT_PAIRS = True   # False (a test seam): the atrous pairs through the im2col operand
 
 
 def conv7s2_index_maps(cin, cout):
@@ -363,7 +360,7 @@ class AdapnetTrainer(object):
                     ops.conv2d_bwd_filter(xact, dz, dw, G(scope, 'bias') if has_bias else None, k, workspace=wws)
                     scatter(dw)
                 if xname is not None:
-                    prev = self._grads.get(xname) if _FUSE_ACCUM else None
+                    prev = self._grads.get(xname)
                     if prev is not None:
                         # a gradient of this tensor already exists (the other branch of a residual block): the data-gradient
                         # conv adds it in its own epilogue -- fp32 sum, one rounding -- instead of an add pass over three maps

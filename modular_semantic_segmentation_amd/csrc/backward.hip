@@ -2,7 +2,6 @@
 // (gfx950).  Together with conv_wgrad.hip and the dgrad mode of conv_mfma.hip these replace the
 // gradient ops that tf.train.{Adam,RMSProp,Adagrad}Optimizer.minimize(self.loss) builds over the
 // training graph of SimpleFCN (base_model.py:153-162, simple_fcn.py:200-214).
-#include <stdlib.h>
 
 #include "xv_common.h"
 
@@ -868,21 +867,14 @@ extern "C" int xv_decoder_head_bwd(const xv_act* fused, const float* w_score, co
 // conv_wgrad.hip: the bf16-split form (maps that tile in 8x32 pixels); the grid it launches, < 0 where it does not apply
 int xv_launch_first_wgrad_split(const float* x, const void* dy, float* dw, float* db, int n, int h, int w, int cin, float* part,
                                 int query_only, hipStream_t stream);
-static bool first_wgrad_split_ok() {
-  static const bool on = getenv("XV_FIRST_WGRAD_OLD") == nullptr &&
-                         (getenv("XV_FIRST_WGRAD_SPLIT") == nullptr || atoi(getenv("XV_FIRST_WGRAD_SPLIT")) != 0);
-  return on;
-}
 
 static void first_wgrad_geometry(int64_t npix, int w, int cin, bool& mfma, unsigned& grid, int& per) {
-  static const bool use_old = getenv("XV_FIRST_WGRAD_OLD") != nullptr;  // the packed-FMA kernel (A/B timing)
-  mfma = !use_old && (w & 3) == 0 && npix * cin < 0x7ff00000;
+  mfma = (w & 3) == 0 && npix * cin < 0x7ff00000;
   if (mfma) {
     // 4 workgroups of 8 waves per CU (a bounded grid: each ends with (9 cin + 1) * 64 partial sums); 16 images at
     // 768x384: 317 us RGB / 181 us depth (packed-FMA kernel: 537 / 340); widths that are not a multiple of 4 keep that kernel
     const int64_t nquads = (npix + 3) / 4;
-    static const int per_cu = getenv("XV_FIRST_WGRAD_PER_CU") ? atoi(getenv("XV_FIRST_WGRAD_PER_CU")) : 4;
-    int64_t blocks = (int64_t)xv_num_cus() * (per_cu > 0 ? per_cu : 4);
+    int64_t blocks = (int64_t)xv_num_cus() * 4;
     if (blocks * 8 * 4 > nquads) blocks = (nquads + 31) / 32;
     int64_t qpw = (nquads + blocks * 8 - 1) / (blocks * 8);
     qpw = (qpw + 3) / 4 * 4;
@@ -903,7 +895,7 @@ extern "C" size_t xv_conv2d_first_bwd_filter_workspace_bytes(int n, int h, int w
   unsigned grid;
   int per;
   first_wgrad_geometry((int64_t)n * h * w, w, cin, mfma, grid, per);
-  const int gs = first_wgrad_split_ok() ? xv_launch_first_wgrad_split(nullptr, nullptr, nullptr, nullptr, n, h, w, cin, nullptr, 1, nullptr) : -1;
+  const int gs = xv_launch_first_wgrad_split(nullptr, nullptr, nullptr, nullptr, n, h, w, cin, nullptr, 1, nullptr);
   if (gs > (int)grid) grid = (unsigned)gs;
   return (size_t)grid * (9 * cin + 1) * 64 * sizeof(float);
 }
@@ -928,8 +920,8 @@ extern "C" int xv_conv2d_first_bwd_filter_ws(const float* x, int n, int h, int w
     XV_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && dbias != nullptr);
     part = (float*)workspace;
   }
-  // the bf16-split form on maps that tile in 8x32 pixels (XV_FIRST_WGRAD_SPLIT=0: the fp32 matrix instruction everywhere)
-  const int gs = first_wgrad_split_ok() ? xv_launch_first_wgrad_split(x, g, dw_hwio, dbias, n, h, w, cin, part, 0, s) : -1;
+  // the bf16-split form on maps that tile in 8x32 pixels; the fp32 matrix instruction elsewhere
+  const int gs = xv_launch_first_wgrad_split(x, g, dw_hwio, dbias, n, h, w, cin, part, 0, s);
   if (gs == -2) return XV_EINVAL;
   if (gs > 0) {
     grid = (unsigned)gs;

@@ -2287,9 +2287,8 @@ extern "C" int xv_score_dense_fwd(const xv_act* u, const float* w_score, const f
   XV_CHECK_SHAPE((u->c & 7) == 0 && u->c <= 256 && num_classes >= 1 && num_classes <= 32);
   const int64_t npix = (int64_t)u->n * u->h * u->w;
   hipStream_t s = (hipStream_t)stream;
-  // the matrix-core form for the FCN's head (64 channels, at most 16 classes); XV_SCORE_DENSE_OLD=1: the FMA kernels (A/B)
-  static const bool sd_old = getenv("XV_SCORE_DENSE_OLD") != nullptr;
-  if (u->c == 64 && num_classes <= 16 && npix < 0x7fff0000 && !sd_old) {
+  // the matrix-core form for the FCN's head (64 channels, at most 16 classes); the FMA kernels elsewhere
+  if (u->c == 64 && num_classes <= 16 && npix < 0x7fff0000) {
     hipLaunchKernelGGL(score_dense_mfma_kernel<2>, dim3(bn_grid(npix / 4 + 1, 2048)), dim3(256), 0, s, (const __bf16*)u->data,
                        w_score, b_score, score, u->n, u->h, u->w, num_classes);
     return xv_launch_status();
@@ -2360,10 +2359,6 @@ static unsigned score_dense_wgrad_grid(int64_t npix, int& qpw) {
 // conv_wgrad.hip: the bf16-split form (64 units, C <= 16, maps that tile in 8x32); the grid it launches, < 0: does not apply
 int xv_launch_score_wgrad_split(const float* ds, const void* y, int n, int h, int w, int c, float* part, int query_only,
                                 hipStream_t stream);
-static bool score_wgrad_split_ok() {
-  static const bool on = getenv("XV_SCORE_WGRAD_SPLIT") == nullptr || atoi(getenv("XV_SCORE_WGRAD_SPLIT")) != 0;
-  return on;
-}
 extern "C" size_t xv_score_dense_bwd_workspace_bytes(int n, int h, int w) {
   if (!xv_dims_sane(n, h, w) || (int64_t)n * h * w >= 0x7fff0000) return 0;
   int qpw;
@@ -2398,15 +2393,13 @@ extern "C" int xv_score_dense_bwd_ws(const xv_act* u, const float* dscore, const
   const size_t lds = (size_t)SD_TILE * (u->c + 8) * 2;
   const unsigned gd = (unsigned)bn_grid(npix, 2048);
   const unsigned gm = (unsigned)bn_grid(npix / 2 + 1, 2048);
-  static const bool sd_old = getenv("XV_SCORE_DENSE_OLD") != nullptr;
-  const bool mfma_dgrad = u->c == 64 && num_classes <= 16 && !sd_old;  // exact fp32 on v_mfma_f32_16x16x4_f32
-  static const bool wg_old = getenv("XV_SCORE_WGRAD_OLD") != nullptr;
+  const bool mfma = u->c == 64 && num_classes <= 16;  // exact fp32 on v_mfma_f32_16x16x4_f32; the FMA kernels elsewhere
   // filter gradient: at most 512 workgroups (each ends with ~800 same-address atomics); a wave walks a contiguous run
   int qpw;
   const unsigned gwm = score_dense_wgrad_grid(npix, qpw);
   hipStream_t s = (hipStream_t)stream;
   float* part = nullptr;
-  if (workspace != nullptr && mfma_dgrad && !wg_old) {
+  if (workspace != nullptr && mfma) {
     if (workspace_bytes < xv_score_dense_bwd_workspace_bytes(u->n, u->h, u->w)) return XV_EWORKSPACE;
     XV_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
     part = (float*)workspace;
@@ -2415,8 +2408,8 @@ extern "C" int xv_score_dense_bwd_ws(const xv_act* u, const float* dscore, const
   {                                                                                                                  \
     static bool attr[XV_MAX_DEVICES] = {false};                                                                      \
     (void)xv_allow_dynamic_lds(reinterpret_cast<const void*>(&score_dense_dgrad_kernel<CMV>), 160 * 1024, attr, false);      \
-    const int gs = (part != nullptr && score_wgrad_split_ok())                                                       \
-                       ? xv_launch_score_wgrad_split(dscore, u->data, u->n, u->h, u->w, num_classes, part, 0, s) : -1;  \
+    const int gs =                                                                                                   \
+        part != nullptr ? xv_launch_score_wgrad_split(dscore, u->data, u->n, u->h, u->w, num_classes, part, 0, s) : -1; \
     if (gs == -2) return XV_EINVAL;                                                                                  \
     if (gs > 0) {                                                                                                    \
       double* const tot = reinterpret_cast<double*>(part + (size_t)gs * 17 * 64);                                    \
@@ -2424,7 +2417,7 @@ extern "C" int xv_score_dense_bwd_ws(const xv_act* u, const float* dscore, const
                          (float*)nullptr, (float*)nullptr);                                                          \
       hipLaunchKernelGGL(score_dense_wgrad_split_scatter_kernel, dim3(1), dim3(256), 0, s, (const double*)tot,         \
                          num_classes, dw_score, db_score);                                                           \
-    } else if (mfma_dgrad && !wg_old) {                                                                              \
+    } else if (mfma) {                                                                                               \
       hipLaunchKernelGGL(score_dense_wgrad_mfma_kernel<8>, dim3(gwm), dim3(256), 0, s, (const __bf16*)u->data, dscore, \
                          dw_score, db_score, u->n, u->h, u->w, num_classes, qpw, part);                               \
       if (part != nullptr) {                                                                                         \
@@ -2438,7 +2431,7 @@ extern "C" int xv_score_dense_bwd_ws(const xv_act* u, const float* dscore, const
       hipLaunchKernelGGL(score_dense_wgrad_kernel<CMV>, dim3(gw), dim3(256), 0, s, (const __bf16*)u->data, dscore,    \
                          dw_score, db_score, u->n, u->h, u->w, u->c, num_classes, per_block);                         \
     }                                                                                                                \
-    if (mfma_dgrad) {                                                                                                \
+    if (mfma) {                                                                                                      \
       if (num_classes <= 12)                                                                                         \
         hipLaunchKernelGGL((score_dense_dgrad_mfma_kernel<4, 3>), dim3(gm), dim3(256), 0, s, dscore, w_score,          \
                            (__bf16*)du->data, u->n, u->h, u->w, num_classes);                                         \

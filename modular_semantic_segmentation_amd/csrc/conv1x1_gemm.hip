@@ -622,13 +622,12 @@ int xv_launch_conv1x1_gemm(const __bf16* x, const __bf16* wpk, const float* bias
     // the wide form wherever the launch makes at least a quarter of a round of its workgroups (the whole AdapNet step, 16 images,
     // one box, alternating: 1 500 images/s without it, 1 574 with a three-quarter-round rule, 1 600 everywhere -- although
     // ALONE on the chip it is the slower form on most short sums, profiles/r6_conv1x1_wide_ab.txt: in the network two experts'
-    // launches share the chip); XV_GEMM_WIDE=0 / 1: never / wherever the shape allows (A/B timing).  Same bits either way.
-    static const int wide_env = getenv("XV_GEMM_WIDE") != nullptr ? atoi(getenv("XV_GEMM_WIDE")) : -1;
+    // launches share the chip).  Same bits either way.
     const int64_t m_wide = (a.Mp + B_BM - 1) / B_BM;
     const int64_t nblk_wide = m_wide * a.n_tiles;
     const bool fits = nblk_wide <= 0x7fffffff && a.Mp + B_BM <= 0x7fffffff && (int64_t)B_BM * Cin * 2 <= 0x7fffffff;
     const bool enough = 4 * nblk_wide >= (int64_t)xv_num_cus();   // at least a quarter of a round: below that, more and smaller workgroups
-    if (fits && wide_env != 0 && (wide_env == 1 || enough)) {
+    if (fits && enough) {
       a.nblk = (int)nblk_wide;
       static bool attr_w[XV_MAX_DEVICES] = {false};
       const hipError_t e = xv_allow_dynamic_lds(reinterpret_cast<const void*>(conv1x1_gemm_wide_kernel<0>), B_LDS_BYTES, attr_w);

@@ -1,6 +1,5 @@
 // conv1_1 of the FCN for gfx950, fp32 image in, bf16 / e4m3 padded-NHWC out: the FMA kernel and the matrix-core kernel
 // (the only file built with -mllvm -amdgpu-mfma-vgpr-form, see the Makefile).
-#include <stdlib.h>
 
 #include "xv_common.h"
 
@@ -346,9 +345,8 @@ extern "C" int xv_conv2d_first_gather7s2_fwd(const float* x, int n, int h, int w
   XV_CHECK_SHAPE(n > 0 && h > 0 && w >= 16 && (cin == 1 || cin == 3) && (w & 15) == 0 && (h & 1) == 0 &&
                  (int64_t)n * h * w * cin < 0x7ff00000);
   XV_CHECK_SHAPE(z->n == n && z->h == h / 2 && z->w == w / 2 && z->c == 576);
-  static const int per_cu = getenv("XV_FIRST_WG_PER_CU") ? atoi(getenv("XV_FIRST_WG_PER_CU")) : 4;
   const int64_t ntiles = (int64_t)n * h * (w / 16);
-  const int64_t want = (ntiles + 3) / 4, cap = (int64_t)xv_num_cus() * (per_cu > 0 ? per_cu : 4);
+  const int64_t want = (ntiles + 3) / 4, cap = (int64_t)xv_num_cus() * 4;  // four workgroups per CU, as xv_conv2d_first_fwd
   const int64_t g0 = want < cap ? want : cap;
   const int tpw = (int)((ntiles + g0 * 4 - 1) / (g0 * 4));
   const unsigned g2 = (unsigned)((ntiles + (int64_t)tpw * 4 - 1) / ((int64_t)tpw * 4));
@@ -376,17 +374,14 @@ extern "C" int xv_conv2d_first_fwd(const float* x, int n, int h, int w, int cin,
   const unsigned grid = (unsigned)((npair + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
   __bf16* yp = (__bf16*)y->data;
-  // The MFMA form takes whole 16-pixel tiles and 32-bit float offsets into x; XV_FIRST_OLD=1 keeps the FMA kernel
-  // (A/B timing), XV_FIRST_WG_PER_CU sizes the persistent grid.
-  static const bool use_old = getenv("XV_FIRST_OLD") != nullptr;
-  if ((cin == 1 || cin == 3) && (w & 15) == 0 && (int64_t)n * h * w * cin < 0x7ff00000 && (!use_old || out8)) {
+  // The MFMA form takes whole 16-pixel tiles and 32-bit float offsets into x; every other shape keeps the FMA kernel.
+  if ((cin == 1 || cin == 3) && (w & 15) == 0 && (int64_t)n * h * w * cin < 0x7ff00000) {
     // 98 VGPRs: five workgroups resident per CU; measured at 8 x 384 x 768 with grid-stride tiles: 5 per CU (one round)
     // 78 / 102 us (depth / RGB), 8: 70 / 92, 16: 65 / 92, 32: 67 / 98, 64: 83 / 122; with contiguous runs per wave 8 per CU:
     // 59 / 84, 16: 62 / 96, 32: 71 / 101; 4 or 5 per CU (all resident, one round): 57 / 83; 3: 88 / 100; 6 (one more than
     // fits): 71 / 97.  4: still one round if a rebuild needs a few more registers
-    static const int per_cu = getenv("XV_FIRST_WG_PER_CU") ? atoi(getenv("XV_FIRST_WG_PER_CU")) : 4;
     const int64_t ntiles = (int64_t)n * h * (w / 16);
-    const int64_t want = (ntiles + 3) / 4, cap = (int64_t)xv_num_cus() * (per_cu > 0 ? per_cu : 4);
+    const int64_t want = (ntiles + 3) / 4, cap = (int64_t)xv_num_cus() * 4;
     const int64_t g0 = want < cap ? want : cap;
     const int tpw = (int)((ntiles + g0 * 4 - 1) / (g0 * 4));               // tiles per wave
     const unsigned g2 = (unsigned)((ntiles + (int64_t)tpw * 4 - 1) / ((int64_t)tpw * 4));

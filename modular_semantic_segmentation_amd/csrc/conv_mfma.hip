@@ -12,7 +12,6 @@
 //   staged ONCE in LDS and re-read by all 9 taps; the 64*NW x 64 weight tile of each tap is
 //   double-buffered.  Pixel rows / weight rows are 128 B in LDS with a 16-byte-slot XOR swizzle
 //   (xv_swz) so the 16-lane ds_read_b128 groups are bank-conflict free.
-#include <cstdlib>
 #include <type_traits>
 
 #include "xv_common.h"
@@ -80,7 +79,6 @@ struct ConvArgs {
   int in_f8, out_f8;
   int scale_x;    // E8M0 byte (127 + scale_exp of x) in all four bytes: the uniform block scale of the B operand
   float out_mul;
-  int debug_same_patch;  // 0 except in -DXV_CONV_EXPERIMENTS tuning builds (configuration 21 only, see launch_conv_dma2)
   // generation 2, stream-K tail (see conv_dma_kernel): workspace of xv_conv2d_streamk_workspace_bytes() -- arrival counters
   // (zero between launches) + fp32 partial-tile slabs -- or null: every tile is computed whole by one workgroup
   char* sk_ws;
@@ -98,7 +96,7 @@ constexpr int XV_SK_MAX_SPLIT = 4;
 // Is the stream-K tail worth it for one XCD group's last round -- `rem` tiles of `nchunks` items on `nb` workgroups, slabs
 // of `slab_kb` KB?  Returns the number of workgroups that share the tail's items (at most XV_SK_MAX_SPLIT per tile: the
 // last arriver reads every other contributor's slab at 60-70 GB/s), or 0 for "compute every tile whole".  Measured on
-// MI355X (bench.py --layer-profile, with / without XV_DMA_NO_STREAMK): an item takes ~2.9 us; the exchange costs ~8 us of
+// MI355X (bench.py --layer-profile, with and without the tail split): an item takes ~2.9 us; the exchange costs ~8 us of
 // latency chain (drain of the write-through stores, ticket, slab reads, one more epilogue) plus its bytes, written through
 // and read back across XCDs, at ~2 TB/s chip-wide -- conv5_x at one image: 9 MB, 46 -> 27 us per launch; conv4_2 at one
 // image: 32 MB, 47 -> 51 us; the half-round tails at 16 images: 24-32 MB for 8 items saved, no gain.  Hence: only where
@@ -303,7 +301,7 @@ __global__ __launch_bounds__(64 * WR * WC * NW, OCC) void conv_mfma_kernel(ConvA
   using C = ConvCfg<MT, WR, WC, NW, KS, TPS>;
   constexpr int ESZ = F8 ? 1 : 2;  // bytes per activation element
   // (fp8: fragments are twice as wide and the cross-item prefetch no longer fits 256 registers -- it spilled 500+)
-  // F8 == 2: the fp8 kernel WITH the prefetch (tuning variant, XV_F8_PFA=1)
+  // (F8 == 2 would be the fp8 kernel WITH the prefetch: a tuning variant no launcher instantiates)
   constexpr bool PFA = (F8 != 1) && ((MT == 4) || (OCC == 1));
   constexpr int PFD = XV_CONV_PFD;  // how many stages before the end of an item its successor's patch is requested
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -326,7 +324,6 @@ __global__ __launch_bounds__(64 * WR * WC * NW, OCC) void conv_mfma_kernel(ConvA
   const char* const wimg = reinterpret_cast<const char*>(a.wpk) + (F8 ? 256 : 0);
   int scale_w = 0;
   if constexpr (F8) scale_w = ((127 + *reinterpret_cast<const int*>(a.wpk)) & 0xff) * 0x01010101;
-  const bool f8_prio = !(a.debug_same_patch & 32);  // (bit 5: XV_F8_NO_PRIO, A/B timing)
 
   // ---- this workgroup's share of the tile list (XCD-aware, placement affects speed only) --------
   // workgroups b, b+8, ... share an XCD (round-robin dispatch); each XCD owns a contiguous range of
@@ -564,10 +561,10 @@ __global__ __launch_bounds__(64 * WR * WC * NW, OCC) void conv_mfma_kernel(ConvA
               for (int j = 0; j < 4; ++j) {
                 acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cat(wlo[j], whi[j]), xf, acc[i][j], 0, 0, 0,
                                                                             scale_w, 0, a.scale_x);
-                if (i == 0 && j == 0 && f8_prio) __builtin_amdgcn_s_setprio(2);
+                if (i == 0 && j == 0) __builtin_amdgcn_s_setprio(2);
               }
             }
-            if (f8_prio) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             // An MFMA is a pure value to the instruction selector: nothing orders it against the (chained) asm reads of
             // the next tap, and it sank below them -- every tap's fragments then lived until the end of the item.  An
             // empty asm that "modifies" each accumulator pins this tap's MFMAs in front of the next tap's reads.
@@ -625,8 +622,6 @@ template <int MT, int WR, int WC, int NW, int KS, int OCC, int TPS = 1, int DMAB
 int launch_conv(const ConvArgs& a0, hipStream_t stream) {
   using C = ConvCfg<MT, WR, WC, NW, KS, TPS>;
   ConvArgs a = a0;
-  static const bool f8_no_prio = getenv("XV_F8_NO_PRIO") != nullptr;
-  if (F8 && f8_no_prio) a.debug_same_patch |= 32;
   a.tiles_x = (a.W + C::TW - 1) / C::TW;
   a.tiles_y = (a.H + C::TH - 1) / C::TH;
   a.n_ct = a.Cout / C::BN;
@@ -1036,7 +1031,7 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void conv_dma_kernel(ConvArgs a) {
   constexpr int RTAIL = 2 * MT > A_TAPS ? 2 * MT - A_TAPS : 0;
   static_assert(RTAIL != YTAIL && RTAIL != 2 * MT, "the counted waits must differ");
   // (a stream-K tail may start a unit at chunk 1: no fixed chunk <-> buffer parity then)
-  const bool resident = nchunks == 2 && (nb % a.n_ct) == 0 && !sk && !(a.debug_same_patch & 8);  // (bit 3: XV_DMA_NO_RESIDENT, A/B timing)
+  const bool resident = nchunks == 2 && (nb % a.n_ct) == 0 && !sk;
   int items_done = 0;
 
   if (nunits == 0) return;
@@ -1378,8 +1373,6 @@ int launch_conv_dma(const ConvArgs& a0, hipStream_t stream) {
   using C = DmaCfg<WR, WC, MT>;
   if (MT % 2 != 0 && a0.pooled != nullptr) return XV_ESHAPE;  // the fused pool pairs rows inside a wave
   ConvArgs a = a0;
-  static const bool no_resident = getenv("XV_DMA_NO_RESIDENT") != nullptr;
-  if (no_resident) a.debug_same_patch |= 8;
   // second half of the packed buffer: the 32-channel-chunk image
   a.wpk = a0.wpk + (int64_t)9 * a.Cin * a.Cout;
   a.tiles_x = (a.W + C::TW - 1) / C::TW;
@@ -1396,12 +1389,9 @@ int launch_conv_dma(const ConvArgs& a0, hipStream_t stream) {
   if ((int64_t)(C::HH * (a.W + 2) + C::HW) * a.Cin * 2 > 0x7fffffff) return XV_ESHAPE;  // 32-bit patch offsets
   a.n_tiles = (int)ntiles;
   const int64_t slots = a.num_cus;
-  static const bool no_sk = getenv("XV_DMA_NO_STREAMK") != nullptr;  // (A/B timing)
-  if (no_sk || a.Cin < 64 || (slots & 7) != 0 || slots > XV_SK_MAX_CUS) a.sk_ws = nullptr;
+  if (a.Cin < 64 || (slots & 7) != 0 || slots > XV_SK_MAX_CUS) a.sk_ws = nullptr;
   // with a stream-K workspace every CU gets a workgroup: the kernel deals the items of an incomplete round out evenly
   const int64_t nblk = a.sk_ws != nullptr ? slots : (ntiles < slots ? ntiles : slots);
-  static const bool grid_only = getenv("XV_SK_GRID_ONLY") != nullptr;  // (experiment: the full grid without the tail split)
-  if (grid_only) a.sk_ws = nullptr;
   hipLaunchKernelGGL((conv_dma_kernel<WR, WC, PRIO, MT>), dim3((unsigned)nblk), dim3(C::NT), C::LDS_BYTES + XV_TRACE_LDS, stream, a);
   return xv_launch_status();
 }
@@ -1662,15 +1652,14 @@ int pick_cfg(const ConvArgs& a, int k) {
   };
   const double g1 = covered(14) < covered(15) ? covered(14) : covered(15);
   if (a.in_f8 || a.out_f8) {
-    // generation 4 wherever the map tiles exactly in 16x32 (XV_F8_NO_GEN4=1: first generation everywhere, A/B timing)
-    static const bool no_gen4 = getenv("XV_F8_NO_GEN4") != nullptr;
+    // generation 4 wherever the map tiles exactly in 16x32
     // (partial tiles: only where the 16x32 tile covers the map well enough -- or where nothing else exists: 64-channel
     // e4m3 chunks)
-    if (k == 3 && a.in_f8 && a.out_f8 && !no_gen4 && xv_conv3x3_f8_dma_ok(a.H, a.W, a.Cin, a.Cout) &&
+    if (k == 3 && a.in_f8 && a.out_f8 && xv_conv3x3_f8_dma_ok(a.H, a.W, a.Cin, a.Cout) &&
         (xv_conv3x3_dma4_exact(a.H, a.W) || (a.Cin & 127) || covered(16) <= 1.3 * g1))
       return 24;
     // the bf16 conv that writes the first e4m3 map: generation 2 has no e4m3 epilogue, generation 4 does
-    if (k == 3 && !a.in_f8 && a.out_f8 && !no_gen4 && xv_conv3x3_dma4_bf16_ok(a.H, a.W, a.Cin, a.Cout)) return 26;
+    if (k == 3 && !a.in_f8 && a.out_f8 && xv_conv3x3_dma4_bf16_ok(a.H, a.W, a.Cin, a.Cout)) return 26;
     if (a.in_f8 && (a.Cin & 127)) return -1;  // 64-channel e4m3 chunks: generation 4 only
     // 16x32 patch, 8 waves, five taps per barrier where it tiles the map (large maps); else two 4-wave workgroups
     if (k == 3 && covered(16) <= g1 && (int64_t)a.N * a.H * a.W >= XV_F8_BIG_MAP) return 16;
@@ -1690,10 +1679,8 @@ int pick_cfg(const ConvArgs& a, int k) {
       // From two rounds of workgroups on, the WORK decides, not the round count: the experts of a fusion model run on two
       // streams and the other expert's workgroups fill an incomplete last round (conv4_x at 16 images: 4.5 rounds of
       // 16x32 tiles against 6 even rounds of the slower 24x16 tile -- the same time one expert alone, 1.5-3.6 % of the
-      // whole two-stream step in favour of the 16x32 tile; XV_CFG_ROUNDS=1 restores the round count for A/B timing).
-      // Below two rounds a launch is latency: the rounds decide.
-      static const bool by_rounds = getenv("XV_CFG_ROUNDS") != nullptr;
-      if (!by_rounds && items >= 2 * (int64_t)a.num_cus) rounds = (double)items / a.num_cus;
+      // whole two-stream step in favour of the 16x32 tile).  Below two rounds a launch is latency: the rounds decide.
+      if (items >= 2 * (int64_t)a.num_cus) rounds = (double)items / a.num_cus;
       const int nchunks = a.Cin / 32;
       if (a.sk_ws != nullptr && items % a.num_cus && (a.num_cus & 7) == 0) {
         // stream-K tail (conv_dma_kernel): the last round's items dealt out over nbp workgroups per XCD group
@@ -1710,35 +1697,22 @@ int pick_cfg(const ConvArgs& a, int k) {
     // 32x32x16 form (25) holds 1.69-1.76 GHz, this one 1.89-1.98 GHz at 3 % more cycles, generation 2 (17: 16x16x32 too, a
     // 15 % longer loop) 1.99-2.12 GHz; on zeros all three run at 2.39 GHz.  26 is ahead of both on every layer shape
     // (profiles/r4_conv_mfma_shape_ab.txt: +7-10 % on conv3_x / conv4_x, +2-8 % on the one- and two-chunk layers).
-    // XV_BF16_GEN4=0: never; =2: only from 128 input channels (A/B timing).
     {
-      static const int gen4 = getenv("XV_BF16_GEN4") != nullptr ? atoi(getenv("XV_BF16_GEN4")) : 1;
-      // (the data-gradient epilogue -- addend + relu mask -- exists in the 16x16 forms: XV_DGRAD_GEN4=0 keeps those convs on
-      // generation 2, A/B timing)
-      static const bool dgrad4 = getenv("XV_DGRAD_GEN4") == nullptr || atoi(getenv("XV_DGRAD_GEN4")) != 0;
+      // (the data-gradient epilogue -- addend + relu mask -- exists in the 16x16 forms too, but not beside a fused pool)
       const bool dg = a.mask != nullptr || a.addend != nullptr;
       // With a stream-K workspace (the `streamk` latency option) only launches that fill the chip at least twice take
       // generations 4 / 5 (no tail to split there: conv1_2 .. conv3_3 at one image); the others keep generation 2 and its
       // stream-K tail (conv4_x / conv5_x at one image: 72 / 24 tiles for 256 CUs).
       const int64_t items16 = (int64_t)a.N * ((a.H + 15) / 16) * ((a.W + 31) / 32) * (a.Cout / 64);
       const bool no_tail = a.sk_ws == nullptr || items16 >= 2 * (int64_t)a.num_cus;
-      // (XV_COL_ROUNDS=1, A/B timing: maps that tile both ways take the 24x16 tile when it makes whole rounds of workgroups
-      // and the 16x32 tile does not -- conv4_x at 16 images: 6 rounds against 4.5)
-      static const bool col_rounds = getenv("XV_COL_ROUNDS") != nullptr && atoi(getenv("XV_COL_ROUNDS")) != 0;
-      if (col_rounds && gen4 && (!dg || dgrad4) && no_tail && !a.in_f8 && !a.out_f8 && a.pooled == nullptr &&
-          xv_conv3x3_col_ok(a.H, a.W, a.Cin, a.Cout, 3) && xv_conv3x3_dma4_exact(a.H, a.W)) {
-        const int64_t i26 = (int64_t)a.N * (a.H / 16) * (a.W / 32) * (a.Cout / 64), i27 = (int64_t)a.N * (a.H / 24) * (a.W / 16) * (a.Cout / 64);
-        if (i27 % a.num_cus == 0 && i26 % a.num_cus != 0) return 27;
-      }
-      if (gen4 && (!dg || (dgrad4 && a.pooled == nullptr)) && no_tail && !a.in_f8 && !a.out_f8 &&
-          xv_conv3x3_dma4_bf16_ok(a.H, a.W, a.Cin, a.Cout) && xv_conv3x3_dma4_exact(a.H, a.W) && (gen4 != 2 || a.Cin >= 128)) {
+      if ((!dg || a.pooled == nullptr) && no_tail && xv_conv3x3_dma4_bf16_ok(a.H, a.W, a.Cin, a.Cout) &&
+          xv_conv3x3_dma4_exact(a.H, a.W)) {
         // Latency rule (round 5, batch 1): below two rounds of 16x32 items a launch ends when its last round does, and the
         // 24x16 tile of generation 5 (same loop, same bits) makes more and smaller items -- conv2_1 at one image: 288 items
         // = 2 rounds of 512 pixels against 384 items = 2 rounds of 384; conv3_x / conv4_x: one round either way.
         // tools/conv_tune.py --batch 1: conv2_1 694 against 571 TFLOP/s, conv3_2 974 / 840, conv4_2 578 / 486
-        // (profiles/r5_conv_tune_b1.txt).  The 24x16 tile is ~5 % slower per pixel once the chip is full.  XV_CFG_LATENCY=0: off.
-        static const bool latency_rule = getenv("XV_CFG_LATENCY") == nullptr || atoi(getenv("XV_CFG_LATENCY")) != 0;
-        if (latency_rule && a.pooled == nullptr && a.sk_ws == nullptr && items16 < 2 * (int64_t)a.num_cus &&
+        // (profiles/r5_conv_tune_b1.txt).  The 24x16 tile is ~5 % slower per pixel once the chip is full.
+        if (a.pooled == nullptr && a.sk_ws == nullptr && items16 < 2 * (int64_t)a.num_cus &&
             xv_conv3x3_col_ok(a.H, a.W, a.Cin, a.Cout, 3)) {
           const int64_t items24 = (int64_t)a.N * (a.H / 24) * (a.W / 16) * (a.Cout / 64);
           const double c26 = (double)((items16 + a.num_cus - 1) / a.num_cus) * 512.0;
@@ -1749,9 +1723,7 @@ int pick_cfg(const ConvArgs& a, int k) {
       }
       // maps that tile in 24x16 but not in 16x32 (the 24x48 conv5 maps of a 768x384 input): the same loop on a column of
       // waves, generation 5 -- conv5_1 at 16 images 1 190 against 985 TFLOP/s on generation 2's 24x16 tile (configuration 22)
-      if (gen4 && (!dg || dgrad4) && no_tail && !a.in_f8 && !a.out_f8 && a.pooled == nullptr &&
-          xv_conv3x3_col_ok(a.H, a.W, a.Cin, a.Cout, 3))
-        return 27;
+      if (no_tail && a.pooled == nullptr && xv_conv3x3_col_ok(a.H, a.W, a.Cin, a.Cout, 3)) return 27;
     }
     int g2 = 17;
     double s2 = 1.25;

@@ -1263,8 +1263,7 @@ static int wgrad1_splits_of(int64_t mp, int64_t tiles, int* steps_per_split) {
   return best;
 }
 static bool wgrad1_ok(int64_t mp, int cin, int cout) {
-  static const bool off = getenv("XV_WGRAD_1X1_GEMM") != nullptr && atoi(getenv("XV_WGRAD_1X1_GEMM")) == 0;  // A/B switch
-  return !off && wgrad1_gi(cin, cout) != 0 && mp >= 64 && 64LL * (cin > cout ? cin : cout) * 2 < 0x7fffffffLL;
+  return wgrad1_gi(cin, cout) != 0 && mp >= 64 && 64LL * (cin > cout ? cin : cout) * 2 < 0x7fffffffLL;
 }
 
 // dw[i] += sum_s slab[s][i], splits summed in a fixed order (bitwise reproducible filter gradients)
@@ -1343,14 +1342,9 @@ extern "C" int xv_bias_grad(const xv_act* dy, float* dbias, void* stream) {
   return xv_launch_status();
 }
 
-static int wgrad_default_variant() {
-  const char* e = getenv("XV_WGRAD_VARIANT");  // A/B timing: 1, 2 (round 5's default) or 3
-  const int v = e != nullptr ? atoi(e) : 3;
-  return v >= 1 && v <= 3 ? v : 3;
-}
-static int g_wgrad_variant = wgrad_default_variant();
+static int g_wgrad_variant = 3;
 extern "C" int xv_set_wgrad_variant(int v) {
-  if (v == 0) v = wgrad_default_variant();
+  if (v == 0) v = 3;
   if (v < 1 || v > 3) return XV_EINVAL;
   g_wgrad_variant = v;
   return XV_OK;
@@ -1515,11 +1509,8 @@ extern "C" int xv_conv2d_bwd_filter_ws(const xv_act* x, const xv_act* dy, float*
   const int64_t dw_elems = (int64_t)k * k * a.Cin * a.Cout;
   a.slab = a.bslab = nullptr;
   // With a workspace EVERY partial sum -- the dW blocks of the pixel splits and the bias gradient's -- goes to slabs that a
-  // second kernel adds in a fixed order: bitwise reproducible gradients.  (Round 2 kept fp32 atomics for the layers with
-  // 1-2 block pairs and for the 1x1 layers, where they are a few per cent faster: XV_WGRAD_ATOMICS=1 restores that for
-  // A/B timing.)  Without a workspace: atomics.
-  static const bool atomics_ok = getenv("XV_WGRAD_ATOMICS") != nullptr;
-  if (workspace != nullptr && !(atomics_ok && !(splits > 1 && k == 3 && pairs >= 4))) {
+  // second kernel adds in a fixed order: bitwise reproducible gradients.  Without a workspace: atomics.
+  if (workspace != nullptr) {
     if (workspace_bytes < (size_t)splits * (dw_elems + a.Cout) * sizeof(float)) return XV_EWORKSPACE;
     XV_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
     a.slab = (float*)workspace;

@@ -6,8 +6,6 @@ fp32 first-layer / score weights.  Per image and stream the encoder runs 13 conv
 pool1..pool4 fused into the epilogues of conv1_2/2_2/3_3/4_3), two 1x1 score convs, the x2
 bilinear + add, and ONE fused decoder-head kernel (x8 bilinear + relu + score + softmax + argmax).
 """
-import os
-
 import numpy as np
 import torch
 
@@ -30,9 +28,9 @@ FP8_CONVS = ('conv2_2', 'conv3_1', 'conv3_2', 'conv3_3', 'conv4_1', 'conv4_2', '
 FP8_MAPS = ('conv1_1', 'conv1_2', 'conv2_1') + FP8_CONVS
 
 
-# how calibrate() chooses an activation map's exponent: 'max' (largest magnitude + one bit of headroom) or 'mse' (least squared
-# e4m3 error on the calibration batch; XV_FP8_CALIBRATION for A/B)
-FP8_CALIBRATION = os.environ.get('XV_FP8_CALIBRATION', 'max')
+# how calibrate() chooses an activation map's exponent unless told otherwise: 'max' (largest magnitude + one bit of headroom);
+# calibrate(method='mse') takes the least squared e4m3 error on the calibration batch
+FP8_CALIBRATION = 'max'
 FP8_DEFAULT_START = 'conv2_2'
 # the accuracy-guarded plan (FcnEngine.calibrate_guarded): first e4m3 conv candidates from the deepest plan (most layers on
 # e4m3 operands) to the shallowest; an expert that fails the bound on all of them runs on bf16 operands
@@ -131,13 +129,10 @@ def _fold_bn(variables, layer, kernel, bias):
     return kernel * s, (bias - variables[layer + '/moving_mean']) * s + variables[layer + '/beta']
 
 
-_FUSE_FIRST = os.environ.get('XV_FUSE_FIRST', '1') != '0'
-
-
 # The two experts of a fusion model run the same layer shapes from conv1_2 on.  From this layer on each 3x3 layer of both is
 # ONE launch (ops.conv2d_fwd_pair: whole rounds of workgroups where each expert alone leaves its last round half empty).
-# XV_GROUP_FROM=<layer name> moves the start, XV_GROUP_FROM=0 keeps every launch per expert (A/B timing).
-GROUP_FROM = os.environ.get('XV_GROUP_FROM', 'conv4_1')
+# (A test seam: another layer name moves the start, a name that is no layer keeps every launch per expert -- same bits.)
+GROUP_FROM = 'conv4_1'
 
 
 def group_from_index():
@@ -370,7 +365,7 @@ class FcnEngine(object):
         ch, cw = h, w
         # conv1_1 + conv1_2 + pool1 in one launch straight onto the first e4m3 map (csrc/conv_first_fused.hip, its e4m3-out form:
         # the same bytes as the two kernels) where conv1_2 takes bf16 operands (the default plan) and neither full map is wanted
-        if not keep_all and _FUSE_FIRST and 'conv1_1' not in maps8 and 'conv1_2' not in convs8 and \
+        if not keep_all and 'conv1_1' not in maps8 and 'conv1_2' not in convs8 and \
                 ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
             # (fp8_start behind conv2_1: pool1 stays bf16)
             q = self._act('pool1', n, h // 2, w // 2, 64, **(dict(dtype='fp8', scale_exp=e['conv1_2']) if 'conv1_2' in maps8 else {}))
@@ -435,8 +430,8 @@ class FcnEngine(object):
         first = 1
         # conv1_1 + conv1_2 + pool1 in one launch where neither full-resolution map is wanted (inference): conv1_1 is
         # evaluated straight into conv1_2's LDS patch buffers (csrc/conv_first_fused.hip; the same bits as the two
-        # kernels).  Maps that do not tile in 16x32 -- and XV_FUSE_FIRST=0, A/B timing -- take the two kernels.
-        if not keep_all and _FUSE_FIRST and ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
+        # kernels).  Maps that do not tile in 16x32 take the two kernels.
+        if not keep_all and ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
             q = self._act('pool1', n, h // 2, w // 2, 64)
             if ops.conv_first_pair_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], self.w['conv1_2'],
                                        self.b['conv1_2'], pooled=q):

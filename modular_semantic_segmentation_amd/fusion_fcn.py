@@ -16,7 +16,7 @@ import torch
 from . import ops
 from .base_model import BaseModel
 from .custom_layers import bilinear_filter, dense_deconv_as_conv3x3, is_bilinear_filter
-from .fcn import BN_EPS, ENCODER, _FUSE_FIRST, _fold_bn, padded_units
+from .fcn import BN_EPS, ENCODER, _fold_bn, padded_units
 
 
 def vgg16_variable_shapes(prefix, in_channels):
@@ -115,7 +115,7 @@ class VggTrunk(object):
         L = {}
         ch, cw = h, w
         first = 1
-        if not keep_all and _FUSE_FIRST and ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
+        if not keep_all and ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
             q = self._act('pool1', n, h // 2, w // 2, 64)
             if ops.conv_first_pair_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], self.w['conv1_2'], self.b['conv1_2'],
                                        pooled=q):

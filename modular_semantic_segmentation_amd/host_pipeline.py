@@ -13,7 +13,7 @@ at 768x384 is 75.5 MB in and 37.7 MB of int64 labels out around 4.4 ms of kernel
   collect    a worker thread moves it into the result array while the GPU computes
 
 Ring slots are reused behind events (device side) and futures (host side); nothing here launches a kernel of its own except
-device-to-device copies (hipMemcpyAsync).  XV_HOST_PIPELINE=0 restores the serial path (A/B timing and the equality test)."""
+device-to-device copies (hipMemcpyAsync).  ENABLED = False restores the serial path (the bench record and the equality test)."""
 import os
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-ENABLED = os.environ.get('XV_HOST_PIPELINE', '1') != '0'
+ENABLED = True                  # False: the serial host path of predict / score / fit (the bench record and a test compare both)
 DEPTH = 4                       # input ring slots: two being staged, one uploaded ahead, one being consumed
 _POOL = None
 TRACE = None                    # tools/trace_pipeline.py: a dict collecting seconds the calling thread spent blocked, by cause

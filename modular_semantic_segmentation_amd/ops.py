@@ -4,7 +4,6 @@ PyTorch is plumbing here: it owns device memory and the stream; every arithmetic
 hot path runs in libxview_hip.so.
 """
 import ctypes
-import os
 
 import torch
 
@@ -1160,7 +1159,7 @@ def maxpool2x2_bwd(y, dpooled, dy):
     return dy
 
 
-ROUTED_POOL = os.environ.get('XV_ROUTED_POOL', '1') != '0'     # 0: full maps + xv_maxpool2x2_bwd everywhere (A/B timing)
+ROUTED_POOL = True     # False (a test seam): full maps + xv_maxpool2x2_bwd everywhere -- the same bits
 
 
 def conv2d_fwd_route(x, w_packed, bias, pooled, route):
@@ -1281,8 +1280,6 @@ def conv2d_fwd_stats(x, w_packed, bias, z, st):
     (xv_bn_finalize_from_rows / xv_bn_sums_from_rows), until then st.sums still holds the previous step's values.  Returns
     False (nothing launched) where that kernel does not apply: the caller then runs conv2d_fwd and lets bn_forward take the
     statistics."""
-    if os.environ.get('XV_BN_CONV_STATS') == '0':        # A/B timing: the separate statistics pass
-        return False
     lib = _lib.lib()
     rows = lib.xv_conv2d_stats_rows()
     if getattr(st, 'conv_rows', None) is None or st.conv_rows.numel() < rows * 2 * st.c:
@@ -1439,7 +1436,7 @@ def upsample_raw_fwd(x, factor, y=None):
 
 
 _UPS_WS = {}
-UPS8_BLOCK_SUMS = os.environ.get('XV_UPS8_BLOCK_SUMS', '1') != '0'      # 0: the gather form of the x8 gradient (A/B timing)
+UPS8_BLOCK_SUMS = True      # False (a test seam): the gather form of the x8 gradient
 
 
 def upsample_raw_bwd(dy, factor, dx):
@@ -1468,8 +1465,6 @@ def bn_apply_ups8(low, st, y, relu=True):
 def score_dense_fwd_ups8(low, st, w_score, b_score, num_classes, y, score):
     """y = relu(BN(bilinear_x8(low))) with the batch norm's scale / shift in `st` (bn_forward(ups8_of=low, y=None) before this)
     AND score = y . W + b in one launch.  Returns False -- nothing launched -- where the fused kernel does not take the shape."""
-    if os.environ.get('XV_FUSED_SCORE_UPS8') == '0':        # A/B timing: the apply pass and the score conv as two launches
-        return False
     rc = _lib.lib().xv_score_dense_fwd_ups8(low.xv(), _ptr(st.scale), _ptr(st.shift), _ptr(w_score), _ptr(b_score), num_classes,
                                             y.xv(), _ptr(score), _stream())
     if rc == XV_ESHAPE:

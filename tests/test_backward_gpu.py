@@ -612,7 +612,7 @@ def test_fusion_fcn_training_with_padded_units(ops, tmp_path):
 
 @pytest.mark.parametrize('kind', ['fcn', 'fcn_bn', 'fusion_fcn'])
 def test_filter_gradients_on_their_own_stream_same_bits(ops, tmp_path, monkeypatch, kind):
-    """The three trainers run their filter gradients on a second HIP stream (trainer._WGRAD_STREAM, XV_WGRAD_STREAM): two steps
+    """The three trainers run their filter gradients on a second HIP stream (trainer._WGRAD_STREAM): two steps
     with and without it from the same weights and batch -- loss, gradient buffer and parameters bit-identical (a cross-stream
     race on a gradient map, the slab workspace or the join in front of the optimizer would show here, not as a tolerance
     failure against the oracle)."""

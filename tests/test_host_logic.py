@@ -758,3 +758,80 @@ def test_bench_dump_outputs_fixed_sample_under_the_size_cap(monkeypatch, tmp_pat
         a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
         assert a.size > 0 and np.array_equal(a, b)
     assert np.isin(np.load(tmp_path / 'a' / 'params.npy'), big['params']).all()
+
+
+def _environment_reads():
+    """{variable: [file:line, ...]} of every environment read in csrc/ and in the package; an occurrence of getenv / environ
+    whose variable cannot be read off the same line (a computed name, an alias) is an error: it would hide a switch."""
+    pkg = os.path.dirname(_lib.CSRC)
+    found = {}
+
+    def scan(path, token, patterns, skip=None):
+        for no, line in enumerate(open(path), 1):
+            if skip is not None and skip.match(line):
+                continue
+            uses = len(re.findall(token, line))
+            names = [n for p in patterns for n in re.findall(p, line)]
+            assert len(names) >= uses, '%s:%d reads the environment by a name this test cannot see: %s' % (path, no, line.strip())
+            for n in names:
+                found.setdefault(n, []).append('%s:%d' % (os.path.relpath(path, ROOT), no))
+
+    for name in sorted(os.listdir(_lib.CSRC)):
+        if name.endswith(('.hip', '.h')):
+            scan(os.path.join(_lib.CSRC, name), r'\bgetenv\b', [r'\bgetenv\(\s*"(\w+)"\s*\)'])
+    quoted = r'''['"](\w+)['"]'''
+    for base, _, files in os.walk(pkg):
+        for name in sorted(files):
+            if name.endswith('.py'):
+                scan(os.path.join(base, name), r'\benviron\b|\bgetenv\b',
+                     [r'\benviron\.get\(\s*' + quoted, r'\benviron\[\s*' + quoted + r'\s*\]', r'\bgetenv\(\s*' + quoted,
+                      quoted + r'\s+(?:not\s+)?in\s+(?:os\.)?environ\b'],
+                     skip=re.compile(r'\s*(from\s+os\s+import|import\s+os)\b'))
+    return found
+
+
+def test_environment_reads_are_the_allowlisted_ones():
+    """The library and the package read these environment variables and no others.  A variable left in a shell selects
+    another kernel, grid or graph without a trace in any record, so a new one is added HERE in the same commit, with its
+    reason:
+      XV_DIRICHLET_HEAD_PK, XV_DIRICHLET_FUSE_PK, XV_GATHER_FLAT   csrc/: test_dirichlet*_pk / the gather tests pin the packed
+                                                                   forms to the scalar ones and the row gathers to the flat
+                                                                   ones through exactly these
+      XV_FORCE_REBUILD, XV_ALLOW_STALE_LIB                         _lib.py: build and loader control (XV_LIB, which goes
+                                                                   with them, is read by tools/ only)
+      XVIEW_DATA_BASEPATH                                          datasets/: where the data lives
+      TMPDIR                                                       datasets/: where an in-memory dataset unpacks its archive,
+                                                                   as the reference's readers do; no XV_ switch
+    (XV_BENCH_RAMP_S and XV_NO_POISON live in bench.py and tests/conftest.py, outside the package.)"""
+    allowed = {'XV_DIRICHLET_HEAD_PK', 'XV_DIRICHLET_FUSE_PK', 'XV_GATHER_FLAT', 'XV_FORCE_REBUILD', 'XV_ALLOW_STALE_LIB',
+               'XVIEW_DATA_BASEPATH', 'TMPDIR'}
+    found = _environment_reads()
+    assert set(found) == allowed, {k: found.get(k, 'no longer read') for k in set(found) ^ allowed}
+    in_csrc = {k for k, where in found.items() if any('csrc' in w for w in where)}
+    assert in_csrc == {'XV_DIRICHLET_HEAD_PK', 'XV_DIRICHLET_FUSE_PK', 'XV_GATHER_FLAT'}
+
+
+def test_chooser_and_workspace_geometry_pinned(golden_dir):
+    """xv_conv2d_choose_cfg and the three filter-gradient workspace queries answer what they answered before the A/B
+    environment switches were folded away (tests/golden/make_chooser_golden.py recorded the table from that commit): every
+    conv layer of the BASELINE.json input sizes at 1, 8 and 16 images, k = 1 and 3, flags 0..7, the four dtype pairs.  Host
+    arithmetic, no launch; the one device fact in it is the CU count (256 without a device and on MI355X), recorded in the
+    table -- on another count the table says nothing."""
+    import sys
+    sys.path.insert(0, golden_dir)
+    try:
+        import make_chooser_golden
+    finally:
+        sys.path.remove(golden_dir)
+    want = json.load(open(os.path.join(golden_dir, 'chooser_geometry.json')))
+    handle = _lib.lib()
+    if handle.xv_conv2d_stats_rows() != want['num_cus']:
+        pytest.skip('table recorded at %d CUs, this device has %d' % (want['num_cus'], handle.xv_conv2d_stats_rows()))
+    got = json.loads(json.dumps(make_chooser_golden.record(handle)))
+    assert sorted(got) == sorted(want)
+    for table in sorted(want):
+        if got[table] != want[table]:
+            keys = [k for k in want[table] if got[table].get(k) != want[table][k]] if isinstance(want[table], dict) else []
+            raise AssertionError('%s differs at %d entries, e.g. %s: %s != %s' % (
+                table, len(keys), keys[:1], [got[table].get(k) for k in keys[:1]], [want[table][k] for k in keys[:1]]))
+    assert len(want['choose_cfg']) == 252 and all(len(v) == 32 for v in want['choose_cfg'].values())

@@ -1,7 +1,7 @@
 """The pipelined host boundary (modular_semantic_segmentation_amd/host_pipeline.py) of predict / score / fit -- the API the
 reference's callers use with HOST arrays (xview/models/base_model.py:180-331; its tf.data prefetch: :203-206): pinned
 staging by worker threads, uploads and label downloads on copy streams, the step captured into a hipGraph after two
-same-shape batches.  Same results as the serial path (XV_HOST_PIPELINE=0), bit for bit: labels, confusion matrices, and the
+same-shape batches.  Same results as the serial path (host_pipeline.ENABLED = False), bit for bit: labels, confusion matrices, and the
 weights after training steps."""
 import os
 

@@ -165,7 +165,7 @@ def test_streamk_workspace_contract(ops):
 
 
 def test_streamk_engine_matches_plain_engine(ops):
-    """The FCN expert with and without the workspace (XV_DMA_NO_STREAMK is the library's A/B switch; here the engine's
+    """The FCN expert with and without the workspace (the library splits whenever it is handed one; here the engine's
     workspace is simply withheld): reproducible, and logits within compounded bf16 rounding of the plain engine's at one image, where every layer
     from conv2 on has a split tail."""
     from modular_semantic_segmentation_amd.fcn import FcnEngine

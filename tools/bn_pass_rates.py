@@ -4,7 +4,8 @@
 
 The kernel-trace CSV of `rocprofv3 --kernel-trace` lists launches in dispatch order; the k-th launch of a kernel inside a
 step is always the same layer (backward visits conv5_3 .. conv1_1), so the median duration per (kernel, k mod per_step)
-is that layer's duration.  Run with XV_WGRAD_STREAM=0 (one stream): a kernel's duration is then its own."""
+is that layer's duration.  Take the trace on one stream (tools/train_trace.sh sets trainer._WGRAD_STREAM = False): a kernel's
+duration is then its own."""
 import argparse
 import collections
 import csv

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """conv_dtype='fp32' (the label-exact parity mode) timed like the headline: two SimpleFCN experts + Bayes fusion on
-resident 768x384 RGB-D inputs.  Prints one JSON record.  usage: exact_bench.py [batch] [steps]"""
+resident 768x384 RGB-D inputs.  Prints one JSON record.  usage: exact_bench.py [batch] [steps] [--scalar]
+(--scalar: round 4's vector-ALU conv kernel, fcn_exact.SCALAR_KERNEL -- the A/B baseline)"""
 import json
 import os
 import sys
@@ -14,8 +15,11 @@ import bench  # noqa: E402
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    from modular_semantic_segmentation_amd import fcn_exact
+    fcn_exact.SCALAR_KERNEL = '--scalar' in sys.argv
+    argv = [a for a in sys.argv if a != '--scalar']
+    batch = int(argv[1]) if len(argv) > 1 else 16
+    steps = int(argv[2]) if len(argv) > 2 else 3
     dev = torch.device('cuda', 0)
     net = bench.build_model(dev, 'bayes', 'fcn', batch, 'fp32')
     data = bench.synthetic_batch(dev, batch, 384, 768, seed=5)
@@ -54,7 +58,7 @@ def main():
                       'ms_per_step': round(dt * 1e3, 3), 'images_per_s': round(batch / dt, 2),
                       'conv_tflops': round(fl / dt / 1e12, 2),
                       'conv3x3_tflops_serial': round(sum(f for f, _ in k3) / sum(m for _, m in k3) / 1e9, 2),
-                      'scalar_kernel': os.environ.get('XV_EXACT_SCALAR', '0') == '1'}))
+                      'scalar_kernel': fcn_exact.SCALAR_KERNEL}))
 
 
 if __name__ == '__main__':

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """predict() / score() / fit() over HOST-resident numpy samples (the API the reference's callers use, base_model.py:265-331):
-images/s including the host -> HBM copies and the label fetch.  usage: host_path_bench.py [samples] [batchsize]"""
+images/s including the host -> HBM copies and the label fetch.  usage: host_path_bench.py [samples] [batchsize] [--serial]
+(--serial: host_pipeline.ENABLED = False, the serial host path)"""
 import json
 import os
 import sys
@@ -15,8 +16,11 @@ import bench  # noqa: E402
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-    bs = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    from modular_semantic_segmentation_amd import host_pipeline
+    host_pipeline.ENABLED = '--serial' not in sys.argv
+    argv = [a for a in sys.argv if a != '--serial']
+    n = int(argv[1]) if len(argv) > 1 else 256
+    bs = int(argv[2]) if len(argv) > 2 else 16
     dev = torch.device('cuda', 0)
     net = bench.build_model(dev, 'bayes', 'fcn', bs, 'bf16')
     rng = np.random.default_rng(0)

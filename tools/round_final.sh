@@ -8,7 +8,6 @@ bash $ROOT/tools/bench_records.sh $TAG > $OUT/${TAG}_records.log 2>&1
 bash $ROOT/tools/profile_elementwise.sh $TAG > $OUT/${TAG}_elementwise.log 2>&1
 bash $ROOT/tools/train_trace.sh $TAG > $OUT/${TAG}_train_trace.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-unset XV_WGRAD_STREAM XV_ROUTED_POOL
 TRAIN="python3 $ROOT/bench.py --mode train --steps 3 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-accuracy --no-extra"
 for v in train train_bn; do
   extra=""; [ $v = train_bn ] && extra="--batch-norm"

@@ -6,8 +6,7 @@ TAG=${1:-r6}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-export XV_WGRAD_STREAM=0
-TRAIN="python3 $ROOT/bench.py --mode train --steps 3 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-accuracy --no-extra --no-roofline-pass"
+TRAIN="python3 $ROOT/tools/bench_with.py trainer._WGRAD_STREAM=False -- --mode train --steps 3 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-accuracy --no-extra --no-roofline-pass"
 rm -rf $OUT/${TAG}_wgrad_pmc1 $OUT/${TAG}_wgrad_pmc2
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES -d $OUT/${TAG}_wgrad_pmc1 -o p -- $TRAIN > $OUT/${TAG}_wgrad_pmc1.log 2>&1
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS -d $OUT/${TAG}_wgrad_pmc2 -o p -- $TRAIN > $OUT/${TAG}_wgrad_pmc2.log 2>&1
