@@ -346,7 +346,9 @@ int xv_decoder_head_fwd(const xv_act* fused, const float* w_score, const float* 
 /* General decoder head for a batch norm with a non-zero shift between the x8 deconv and its relu (the default of
  * decoder() as called by fusion_fcn.py:38; custom_layers.py:112-119): upscore = relu(bilinear_x8(fused) * scale[u] +
  * shift[u]), then score / softmax / argmax as above.  The 1x1 conv no longer commutes with the interpolation, so
- * all U features are interpolated per pixel (16x the FMAs of xv_decoder_head_fwd; no workspace).                 */
+ * all U features are interpolated per pixel (16x the FMAs of xv_decoder_head_fwd; no workspace).
+ * `label`, where given, is 16-byte aligned (labels leave in 16-byte pairs; XV_EINVAL otherwise), and n, h, w of `fused`
+ * are positive (XV_ESHAPE otherwise); nothing is written when either check fails.                                  */
 int xv_decoder_head_affine_fwd(const xv_act* fused, const float* scale, const float* shift, const float* w_score,
                                const float* b_score, int num_classes, float* score, float* prob, int64_t* label,
                                void* stream);

@@ -1538,6 +1538,8 @@ extern "C" int xv_decoder_head_affine_fwd(const xv_act* fused, const float* scal
                                          float* prob, int64_t* label, void* stream) {
   XV_REQUIRE_BF16(fused);
   XV_CHECK_ARG(fused && fused->data && scale && shift && w_score && b_score && (score || prob || label));
+  XV_CHECK_ARG(!label || ((uintptr_t)label & 15) == 0);  // the kernel stores labels in 16-byte pairs
+  XV_CHECK_SHAPE(fused->n > 0 && fused->h > 0 && fused->w > 0);
   XV_CHECK_SHAPE(fused->c > 0 && (fused->c & 7) == 0 && num_classes >= 1 && num_classes <= 32);
   const int Wo = fused->w * 8;
   const int64_t nblk = (int64_t)((Wo + 127) / 128) * fused->h * fused->n;

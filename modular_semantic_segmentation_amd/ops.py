@@ -578,6 +578,18 @@ def score_lowres(fused, w_score, num_classes, S):
     return S
 
 
+def decoder_head_from_scores(S, b_score, n, hi, wi, num_classes, score=None, prob=None, label=None):
+    """The second half of decoder_head_fwd on low-resolution scores S (float32 [n][hi+2][wi+2][CP], zero border, e.g. from
+    score_lowres): the x8 interpolation + bias -> whichever of score / prob (float32 [n, 8hi, 8wi, C]) and label (int64
+    [n, 8hi, 8wi]) are given, written in place.  The label alone into a 16-byte aligned buffer runs four pixels per thread."""
+    _need(S, torch.float32, 'S')
+    _need(b_score, torch.float32, 'b_score')
+    rc = _lib.lib().xv_decoder_head_from_scores(_ptr(S), _ptr(b_score), int(n), int(hi), int(wi), int(num_classes), _ptr(score),
+                                               _ptr(prob), _ptr(label), _stream())
+    _lib.check(rc, 'xv_decoder_head_from_scores')
+    return score, prob, label
+
+
 def fused_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, tab, logprior, lognorm=None, out=None):
     """Both experts' low-resolution scores -> the fused label map (int64 [n, 8hi, 8wi]); lognorm given = Dirichlet
     fusion (tab = alpha - 1), else Bayes (tab = log-likelihood tables)."""

@@ -172,7 +172,7 @@ def _check_maps(out, ref, c, T, clear_share):
 # in place of the kernel's hash) for all 15 (C, T) pairs and both kinds: the smallest share is 0.9989 (C = 14, T = 2,
 # 'random'), far above the 0.9 required.
 @pytest.mark.parametrize('kind', ['random', 'dropped'])
-@pytest.mark.parametrize('c', [3, 5, 12, 14, 16])
+@pytest.mark.parametrize('c', [3, 5, 12, 14, 16, 20, 30, 32])
 @pytest.mark.parametrize('T', [1, 2, 7])
 def test_uncertainty_head_against_unfused_path(gpu, c, T, kind):
     from modular_semantic_segmentation_amd import ops

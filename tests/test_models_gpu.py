@@ -560,7 +560,7 @@ def test_fused_head_equals_unfused_path(gpu, tmp_path, golden_dir, kind):
     assert np.array_equal(plain.predict(data), ref)
 
 
-@pytest.mark.parametrize('c', [3, 5, 12, 14, 16])
+@pytest.mark.parametrize('c', [3, 5, 12, 14, 16, 20, 30, 32])
 def test_fused_head_op_equals_decoder_heads_and_fusion_kernels(gpu, c):
     """Op level, for class counts that fill their template (12, 16) and that do not (3, 5, 14): both experts' 1/8-resolution
     features -> xv_score_lowres -> xv_fused_head_fwd against decoder head per expert (labels / probabilities in HBM) ->
@@ -593,7 +593,7 @@ def test_fused_head_op_equals_decoder_heads_and_fusion_kernels(gpu, c):
     assert torch.equal(got, ref)
 
 
-@pytest.mark.parametrize('c', [4, 8, 12, 16])
+@pytest.mark.parametrize('c', [4, 8, 12, 16, 20, 24])
 @pytest.mark.parametrize('shape', [(1, 3, 5), (2, 6, 4), (3, 7, 9)])
 def test_dirichlet_head_packed_form_equals_scalar_form(gpu, c, shape):
     """The fused Dirichlet head for a class count that fills its template (C == CM) runs on packed fp32, four output pixels

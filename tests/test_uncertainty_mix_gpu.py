@@ -236,7 +236,7 @@ def _check_scores(tag, score, label, ref, bound, min_clear):
     assert torch.equal(label[clear], ref.argmax(-1)[clear]), tag
 
 
-@pytest.mark.parametrize('c', [3, 5, 12, 14, 16])
+@pytest.mark.parametrize('c', [3, 5, 12, 14, 16, 20, 30, 32])
 @pytest.mark.parametrize('T', [2, 7])
 def test_uncertainty_moments(gpu, c, T):
     from modular_semantic_segmentation_amd import ops
@@ -266,7 +266,7 @@ def test_uncertainty_moments_identical_samples(gpu, c):
     assert torch.count_nonzero(mvar).item() == 0 and torch.count_nonzero(vmax).item() == 0
 
 
-@pytest.mark.parametrize('c', [3, 5, 12, 14, 16])
+@pytest.mark.parametrize('c', [3, 5, 12, 14, 16, 20, 30, 32])
 @pytest.mark.parametrize('T', [2, 7])
 def test_uncertainty_dirichlet_head(gpu, c, T):
     from modular_semantic_segmentation_amd import ops

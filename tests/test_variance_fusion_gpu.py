@@ -98,7 +98,7 @@ def _clear(score, margin=1e-4):
     return (top2[..., 0] - top2[..., 1]) > margin
 
 
-@pytest.mark.parametrize('c', [3, 5, 12, 14, 16])
+@pytest.mark.parametrize('c', [3, 5, 12, 14, 16, 20, 30, 32])
 @pytest.mark.parametrize('T', [1, 2, 7])
 def test_variance_head_against_unfused_path(gpu, c, T):
     from modular_semantic_segmentation_amd import ops
