@@ -511,6 +511,22 @@ int xv_fused_head_joint_hist_fwd(const float* Sa, const float* Sb, const float* 
                                  int wi, int num_classes, const int32_t* labels, int64_t* hist, int max_workgroups,
                                  void* stream);
 
+/* Fused average head of a two-expert fusion model (average_mix.py:18-21): Sa, Sb, biases, n, hi, wi, num_classes as
+ * xv_fused_head_fwd takes them -> per output pixel both experts' softmax (bits of xv_decoder_head_fwd's prob), their sum
+ * halved, and its first-maximum argmax -> fused_label int64 [n][8hi][8wi] (16-byte aligned): the labels of two
+ * xv_decoder_head_fwd with prob + xv_average_fuse, bit for bit, without the two probability maps.  XV_EINVAL for a null or
+ * misaligned pointer, num_classes outside 1..32 or a width 8 wi a thread's pixel group does not divide.                      */
+int xv_fused_head_average_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                              int wi, int num_classes, int64_t* fused_label, void* stream);
+
+/* Counting form of the fused average head: cm int64 [C][C] (rows = ground truth), cm[label][fused] += 1 over the pixels with
+ * 0 <= label < C (labels int32 [n][8hi][8wi], 16-byte aligned) as xv_confusion_matrix would count xv_fused_head_average_fwd's
+ * labels: accumulated, not cleared; no label map is written.  max_workgroups bounds the grid (0: the kernel's own bound).
+ * XV_EINVAL as xv_fused_head_average_fwd, and for max_workgroups < 0.                                                        */
+int xv_fused_head_average_count_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
+                                    int wi, int num_classes, const int32_t* labels, int64_t* cm, int max_workgroups,
+                                    void* stream);
+
 /* Variance head of the MC-dropout fusion model (variance_mix.py:7-15,33-83): Sa / Sb = xv_score_lowres of each expert's
  * (T+1) n-image map (slot 0 plain, slots 1..T dropout samples; T = num_samples) -> per output pixel and expert the softmax of
  * every pass, the variance over the T samples averaged over the classes, and the certainty-weighted fusion of the plain

@@ -1117,6 +1117,144 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 
   }
 }
 
+// ---- fused average head (average_mix.py:18-21 on the low-resolution class scores) ------------------------------------------
+// Both experts' probabilities per output pixel -- head_load_taps / head_eval_taps / head_max / head_softmax: the bits
+// decoder_head_kernel stores as `prob` -- then average_fuse_kernel's (fusion.hip) statements for two experts: s[k] = pa[k] +
+// pb[k], v = s[k] / 2, first-maximum argmax over k < C.  The labels are those of two decoder heads with `prob` + xv_average_fuse
+// bit for bit, and the two float32 probability maps (2 x 4C bytes per pixel, written and read back) never exist.
+// P = TWO consecutive output pixels per thread on shared taps: a thread holds the 4 CM registers of one expert's taps, the
+// first expert's P CM probabilities and the CM values of the pixel in work, (5 + P) CM in all -- four pixels as in the Bayes
+// head are 108 registers at 12 classes before any address or weight.  The pixels of a group and the two experts are worked
+// through one after the other (empty asm statements that make the next one's input wait for the last result, no instruction):
+// left alone the scheduler interleaves them and every interleaved pixel adds CM live registers (12 classes: 128 registers and
+// 68 to 100 bytes of scratch in the counting form).  At 16 classes 7 CM = 112 registers still leave nothing for the rest, so
+// there the first expert's probabilities wait in LDS (a private 16-byte column per thread and class quad, no barrier).
+// COUNT = false: the label map int64 [N][8Hi][8Wi], one 16-byte store per thread; a grid that covers every pixel group (one
+// trip of the loop).  COUNT = true: cm[label][fused] += 1 over the pixels with 0 <= label < C and no label map: u32 counters
+// [C][C] in LDS through xv_wave_count, a bounded grid with a grid-stride loop whose trip count is uniform over the workgroup
+// (a lane past the end recomputes the last group and counts nothing), one 64-bit global atomic per non-zero cell and
+// workgroup -- the scheme of fused_head_joint_hist_kernel.  FULL: the class count IS CM, every `k < C` folds away.
+constexpr int XV_AVERAGE_PIXELS = 2;
+constexpr bool xv_average_stash(int cm) { return cm == 16; }
+// dynamic LDS of one launch: the counters (counting form), then the stash
+static size_t average_head_lds(int num_classes, bool count) {
+  const int cm = (num_classes + 3) / 4 * 4;
+  return (count ? (size_t)(num_classes * num_classes + 3) / 4 * 16 : 0) +
+         (xv_average_stash(cm) ? (size_t)256 * XV_AVERAGE_PIXELS * cm * 4 : 0);
+}
+
+template <int CM, bool COUNT, bool FULL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 4 : 1))) void fused_head_average_kernel(
+    const float* __restrict__ Sa, const float* __restrict__ Sb, const float* __restrict__ ba, const float* __restrict__ bb, int N,
+    int Hi, int Wi, int C_, int64_t* __restrict__ fused, const int32_t* __restrict__ labels,
+    unsigned long long* __restrict__ cm) {
+  const int C = FULL ? CM : C_;
+  constexpr int P = XV_AVERAGE_PIXELS;
+  constexpr bool STASH = xv_average_stash(CM);
+  constexpr int SR = STASH ? 1 : P;  // rows of the first expert's probabilities kept in registers
+  static_assert(8 % P == 0 && P % 2 == 0, "a pixel group is whole 16-byte stores inside one source column");
+  extern __shared__ __attribute__((aligned(16))) uint32_t av_cnt[];  // COUNT: [C][C]; STASH: f32x4 [P][CM / 4][256] behind it
+  f32x4* stash = reinterpret_cast<f32x4*>(av_cnt + (COUNT ? (C * C + 3) / 4 * 4 : 0)) + threadIdx.x;
+  if constexpr (COUNT) {
+    for (int i = threadIdx.x; i < C * C; i += 256) av_cnt[i] = 0u;
+    __syncthreads();
+  }
+  const int Ho = Hi * 8, Wo = Wi * 8, Wq = Wo / P;
+  const int64_t nquads = (int64_t)N * Ho * Wq;
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < nquads; base += (int64_t)gridDim.x * 256) {
+    const bool live = base + threadIdx.x < nquads;
+    if (__ballot(live) == 0) continue;  // (wave-uniform)
+    const int64_t quad = live ? base + threadIdx.x : nquads - 1;
+    const int ox0 = (int)(quad % Wq) * P;
+    const int oy = (int)((quad / Wq) % Ho);
+    const int n = (int)(quad / ((int64_t)Wq * Ho));
+    int iy1, ix1;
+    float wy1, wy0;
+    bilinear_taps<8>(oy, iy1, wy1, wy0);
+    {
+      float u1, u0;
+      bilinear_taps<8>(ox0, ix1, u1, u0);
+    }
+    float pa[SR][CM];  // the first expert's probabilities (STASH: of the pixel in work)
+    int out[P];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      int ne = n;
+      if (e == 1) asm volatile("" : "+v"(ne) : "v"(pa[SR - 1][CM - 1]));
+      f32x4 ta[CM / 4], tb[CM / 4], tc[CM / 4], td[CM / 4];
+      head_load_taps<CM>(e == 0 ? Sa : Sb, ne, iy1, ix1, Hi, Wi, ta, tb, tc, td);
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int r = STASH ? 0 : p;
+        int ixp;
+        float wx1, wx0;
+        bilinear_taps<8>(ox0 + p, ixp, wx1, wx0);
+        if (p > 0) {
+          if (e == 0)
+            asm volatile("" : "+v"(wx1) : "v"(pa[STASH ? 0 : p - 1][CM - 1]));
+          else
+            asm volatile("" : "+v"(wx1) : "v"(out[p - 1]));
+        }
+        float sc[CM];
+        head_eval_taps<CM>(ta, tb, tc, td, wy1, wy0, wx1, wx0, e == 0 ? ba : bb, C, sc);
+        const float m = head_max<CM>(sc, C);
+        head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
+        if (e == 0) {
+#pragma unroll
+          for (int k = 0; k < CM; ++k) pa[r][k] = sc[k];
+          if constexpr (STASH) {
+#pragma unroll
+            for (int k4 = 0; k4 < CM / 4; ++k4)
+              stash[(p * (CM / 4) + k4) * 256] = f32x4{sc[4 * k4], sc[4 * k4 + 1], sc[4 * k4 + 2], sc[4 * k4 + 3]};
+          }
+        } else {
+          if constexpr (STASH) {
+#pragma unroll
+            for (int k4 = 0; k4 < CM / 4; ++k4) {
+              const f32x4 t = stash[(p * (CM / 4) + k4) * 256];
+              pa[0][4 * k4] = t.x, pa[0][4 * k4 + 1] = t.y, pa[0][4 * k4 + 2] = t.z, pa[0][4 * k4 + 3] = t.w;
+            }
+          }
+          // average_fuse_kernel for two experts: s = pa + pb, v = s / 2, the first maximum
+          float best = 0.f;
+          int bi = 0;
+#pragma unroll
+          for (int k = 0; k < CM; ++k) {
+            const float s = pa[r][k] + sc[k];
+            const float v = s / 2.0f;
+            if (k < C && (k == 0 || v > best)) {
+              best = v;
+              bi = k;
+            }
+          }
+          out[p] = bi;
+        }
+      }
+    }
+    if constexpr (COUNT) {
+      typedef int i32xP __attribute__((ext_vector_type(P)));
+      const i32xP lv = *reinterpret_cast<const i32xP*>(labels + quad * P);
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int l = lv[p];
+        xv_wave_count(av_cnt, (live && l >= 0 && l < C) ? l * C + out[p] : -1);
+      }
+    } else if (live) {
+      typedef __attribute__((ext_vector_type(2))) long long i64x2;
+      int64_t* dst = fused + quad * P;
+#pragma unroll
+      for (int p = 0; p < P; p += 2) *reinterpret_cast<i64x2*>(dst + p) = i64x2{out[p], out[p + 1]};
+    }
+  }
+  if constexpr (COUNT) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < C * C; i += 256) {
+      const uint32_t v = av_cnt[i];
+      if (v) atomicAdd(&cm[i], (unsigned long long)v);
+    }
+  }
+}
+
 // ---- softmax + argmax on dense fp32 scores (basic_fusion_model.py:21-22) -------------------------
 template <int CMAX>
 __global__ __launch_bounds__(256) void softmax_argmax_kernel(const float* __restrict__ score, int64_t npix, int C,
@@ -1421,6 +1559,57 @@ extern "C" int xv_fused_head_joint_hist_fwd(const float* Sa, const float* Sb, co
 #undef XV_JH
   return xv_launch_status();
 }
+
+// Fused average head (see fused_head_average_kernel), label and counting form.  A thread's pixel group (two pixels) must
+// divide the output width 8 wi: it always does, the check stands for whoever changes the group.
+#define XV_FA_LAUNCH(CMV, COUNT, GRID, LDS, FUSED, LABELS, CMP)                                                               \
+  {                                                                                                                          \
+    if (num_classes == CMV)                                                                                                  \
+      hipLaunchKernelGGL((fused_head_average_kernel<CMV, COUNT, true>), dim3(GRID), dim3(256), LDS, s, Sa, Sb, bias_a, bias_b, \
+                         n, hi, wi, num_classes, FUSED, LABELS, CMP);                                                        \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((fused_head_average_kernel<CMV, COUNT, false>), dim3(GRID), dim3(256), LDS, s, Sa, Sb, bias_a,       \
+                         bias_b, n, hi, wi, num_classes, FUSED, LABELS, CMP);                                                \
+  }
+
+extern "C" int xv_fused_head_average_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
+                                         int hi, int wi, int num_classes, int64_t* fused_label, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && fused_label && ((uintptr_t)fused_label & 15) == 0);
+  XV_CHECK_ARG(num_classes >= 1 && num_classes <= 32);
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  const int group = XV_AVERAGE_PIXELS;
+  XV_CHECK_ARG(((int64_t)wi * 8) % group == 0);
+  const int64_t nquads = (int64_t)n * hi * wi * 64 / group;
+  XV_CHECK_SHAPE((nquads + 255) / 256 <= 0x7fffffff);
+  const unsigned grid = (unsigned)((nquads + 255) / 256);
+  const size_t lds = average_head_lds(num_classes, false);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_FA(CMV) XV_FA_LAUNCH(CMV, false, grid, lds, fused_label, (const int32_t*)nullptr, (unsigned long long*)nullptr)
+  XV_CM_SWITCH(num_classes, XV_FA)
+#undef XV_FA
+  return xv_launch_status();
+}
+
+extern "C" int xv_fused_head_average_count_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
+                                               int hi, int wi, int num_classes, const int32_t* labels, int64_t* cm,
+                                               int max_workgroups, void* stream) {
+  XV_CHECK_ARG(Sa && Sb && bias_a && bias_b && labels && cm && ((uintptr_t)labels & 15) == 0);
+  XV_CHECK_ARG(num_classes >= 1 && num_classes <= 32 && max_workgroups >= 0);
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  const int group = XV_AVERAGE_PIXELS;
+  XV_CHECK_ARG(((int64_t)wi * 8) % group == 0);
+  const int64_t nquads = (int64_t)n * hi * wi * 64 / group;
+  const int grid = grid_score_workgroups(nquads, max_workgroups);
+  XV_CHECK_SHAPE(nquads / grid < ((int64_t)1 << 29));  // (a workgroup's u32 counters)
+  const size_t lds = average_head_lds(num_classes, true);
+  hipStream_t s = (hipStream_t)stream;
+#define XV_FA(CMV) \
+  XV_FA_LAUNCH(CMV, true, grid, lds, (int64_t*)nullptr, labels, reinterpret_cast<unsigned long long*>(cm))
+  XV_CM_SWITCH(num_classes, XV_FA)
+#undef XV_FA
+  return xv_launch_status();
+}
+#undef XV_FA_LAUNCH
 
 // Variance head of the MC-dropout fusion model (see variance_head_kernel): Sa / Sb from xv_score_lowres of each expert's
 // (T+1) n-image `fused` map, [(T+1) n][hi+2][wi+2][CP] each.

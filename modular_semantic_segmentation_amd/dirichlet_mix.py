@@ -59,6 +59,26 @@ def dirichlet_fusion(probs, dirichlet_params, prior, sigma=1.0):
     return score
 
 
+def fit_dirichlet_params(counts, class_counts, delta, beta, num_classes, modalities):
+    """dirichlet_mix.py:207-257: {modality: [C,C] parameters} fitted on the host to the sufficient statistics `counts`
+    {modality: [C,C]} and the class counts [C] under one (delta, beta) -- the fit of DirichletFusion and FusionComparison."""
+    C = num_classes
+
+    def dirichlet_em(measurements):
+        params = np.ones((C, C)).astype('float64')
+        for c in range(C):
+            if class_counts[c] == 0:
+                params[:, c] = np.ones(C)
+                continue
+            ss = (measurements[c, :] / class_counts[c]).astype('float64')
+            neg_ss = (measurements.sum(0) - measurements[c, :]) / (class_counts.sum() - class_counts[c])
+            params[:, c] = find_dirichlet_priors(ss, neg_ss, np.ones(C, 'float64'), max_iter=10000,
+                                                 delta=delta, beta=beta)
+        return params
+
+    return {m: dirichlet_em(counts[m]) for m in modalities}
+
+
 class DirichletFusion(BaseModel):
     """config: modalities, num_channels, num_units, expert_model, class_prior, sigma, delta, beta,
     optional dirichlet_params {modality: [C,C], 'class_counts': [C]}; the expert of modality m uses
@@ -153,21 +173,7 @@ class DirichletFusion(BaseModel):
 
     def _dirichlet_em(self, counts, class_counts, delta, beta):
         """{modality: [C,C] parameters} fitted to the sufficient statistics under one (delta, beta)."""
-        C = self.config['num_classes']
-
-        def dirichlet_em(measurements):
-            params = np.ones((C, C)).astype('float64')
-            for c in range(C):
-                if class_counts[c] == 0:
-                    params[:, c] = np.ones(C)
-                    continue
-                ss = (measurements[c, :] / class_counts[c]).astype('float64')
-                neg_ss = (measurements.sum(0) - measurements[c, :]) / (class_counts.sum() - class_counts[c])
-                params[:, c] = find_dirichlet_priors(ss, neg_ss, np.ones(C, 'float64'), max_iter=10000,
-                                                     delta=delta, beta=beta)
-            return params
-
-        return {m: dirichlet_em(counts[m]) for m in self.modalities}
+        return fit_dirichlet_params(counts, class_counts, delta, beta, self.config['num_classes'], self.modalities)
 
     def fit(self, data, *args, **kwargs):
         """Measure the experts against the ground truth of `data`, then fit the class-conditional

@@ -1,6 +1,6 @@
 """The reference's evaluation / fusion experiment flows without the sacred experiment database
 (reference: experiments/evaluation.py:14-41,62-110, experiments/bayes_fusion.py:21-33,146-195,
-experiments/dirichlet_fusion.py:19-81, experiments/training.py, experiments/uncertainty_eval.py:18-52,
+experiments/dirichlet_fusion.py:19-81, average_mix.py, experiments/training.py, experiments/uncertainty_eval.py:18-52,
 experiments/different_evaluation_parameters.py:10-61).
 
 Datasets here are dicts of arrays ({'rgb': [N,H,W,3], 'depth': [N,H,W,1], 'labels': [N,H,W]}) or any iterable of
@@ -16,6 +16,7 @@ from . import get_model
 from .basic_fusion_model import parameter_combinations  # noqa: F401  (the reference's name, defined beside score_grid)
 from .bayes_mix import BayesFusion
 from .dirichlet_mix import DirichletFusion
+from .fusion_comparison import FusionComparison
 
 
 def import_weights_into_network(net, starting_weights, **kwargs):
@@ -102,6 +103,23 @@ def fit_and_evaluate_dirichlet_fusion(net_config, data_description, measure_set,
         info['dirichlet_params'] = net.fit(measure_set)
         import_weights_into_network(net, starting_weights)
         info['measurements'], info['confusion_matrix'] = net.score(test_set)
+    return info
+
+
+def fit_and_evaluate_all_fusions(net_config, data_description, measure_set, test_set, starting_weights):
+    """The table of the two flows above and of an AverageFusion on the same split, from ONE pass of the experts over each half
+    (fusion_comparison.FusionComparison): measure every expert's confusion matrix and the Dirichlet statistics on the
+    measurement set, then score every expert alone and the Bayes, Dirichlet and average fusion on the test set.
+    net_config: a Bayes-fusion config (expert_model, prefixes, num_channels, num_units, class_prior, ...) plus sigma, delta,
+    beta.  Returns {'measurements': {modality: ..., 'bayes_fusion': ..., 'dirichlet_fusion': ..., 'average_fusion': ...},
+    'confusion_matrix': the same keys, 'confusion_matrices': {modality: [C,C]}, 'dirichlet_params': {modality: [C,C],
+    'class_counts': [C]}} -- the last two are what BayesFusion and DirichletFusion take as measurements."""
+    info = {'measurements': {}, 'confusion_matrix': {}}
+    with FusionComparison(data_description=data_description, **net_config) as net:
+        import_weights_into_network(net, starting_weights)
+        info.update(net.fit(measure_set))
+        for name, (measures, confusion_matrix) in net.score_all(test_set).items():
+            info['measurements'][name], info['confusion_matrix'][name] = measures, confusion_matrix
     return info
 
 

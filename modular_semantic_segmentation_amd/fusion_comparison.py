@@ -1,0 +1,152 @@
+"""The reference's central comparison -- every expert alone, Bayes, Dirichlet and average fusion on one test split after
+measuring the experts on the other -- on ONE pass of the experts per split (reference: experiments/bayes_fusion.py:146-195,
+experiments/dirichlet_fusion.py:58-81, average_mix.py; there one model per row of the table).
+
+The fusions differ only in what they do with the experts' outputs, so the trunks run once per batch.  Where the fused head
+serves the model (two FCN experts with commuted heads) they stop at their 1/8-resolution class scores and three scoring heads
+count from those: the joint histogram (both experts' matrices are its marginals, the Bayes matrix follows from the decision
+table on the host), the grid-scoring head with one grid point (Dirichlet) and the counting form of the fused average head.
+Otherwise -- any number of experts, AdapNet experts, fused_head=False, more classes than the joint histogram holds -- the
+experts' labels and probabilities are materialised once and the stand-alone fusion kernels run on them.  Both routes count the
+integers score() of the corresponding single model counts."""
+from copy import deepcopy
+
+import numpy as np
+import torch
+
+from . import ops
+from .base_model import score_measures
+from .basic_fusion_model import FusionModel, _labelled_batches, fused_head_applicable, run_experts, run_lowres_scores
+from .bayes_mix import BayesFusion, bayes_tables, confusion_from_joint_hist, fused_decision_table
+from .dirichlet_mix import DirichletFusion, dirichlet_tables, fit_dirichlet_params
+
+FUSIONS = ('bayes_fusion', 'dirichlet_fusion', 'average_fusion')
+
+
+def expert_matrices_from_joint_hist(hist):
+    """The two experts' confusion matrices [C,C] (rows = ground truth) from hist[label][a][b]: its marginals."""
+    hist = np.asarray(hist)
+    return hist.sum(2), hist.sum(1)
+
+
+class FusionComparison(FusionModel):
+    """config: a Bayes-fusion configuration (prefixes, num_channels, num_units, expert_model, class_prior, ...) plus the
+    Dirichlet fusion's sigma, delta, beta; optional measurements confusion_matrices {modality: [C,C] label x pred} and
+    dirichlet_params {modality: [C,C], 'class_counts': [C]} -- what fit() measures and returns.  The Dirichlet fusion of the
+    reference names an expert's variables by its modality: compare against a DirichletFusion with prefixes {m: m}."""
+
+    def __init__(self, output_dir=None, confusion_matrices=None, dirichlet_params=None, **config):
+        standard_config = {'learning_rate': 0.0, 'class_prior': 'data'}
+        standard_config.update(config)
+        for key in ('sigma', 'delta', 'beta'):
+            if key not in standard_config:
+                raise UserWarning('ERROR: FusionComparison needs %s (the Dirichlet fusion\'s parameter)' % key)
+        self.confusion_matrices = None if not confusion_matrices else \
+            {m: np.asarray(confusion_matrices[m]).astype(np.float64) for m in config['prefixes']}
+        self.dirichlet_params = self.class_counts = None
+        if dirichlet_params:
+            self.dirichlet_params = {m: np.asarray(dirichlet_params[m]).astype('float32') for m in config['prefixes']}
+            self.class_counts = np.asarray(dirichlet_params['class_counts']).astype('float32')
+        FusionModel.__init__(self, 'FusionComparison', output_dir=output_dir, **standard_config)
+
+    def _build_graph(self):
+        FusionModel._build_graph(self)
+        self._build_tables()
+
+    def _build_tables(self):
+        """The tables BayesFusion and DirichletFusion build from the same measurements and config."""
+        self.bayes = self.dirichlet = None
+        if self.confusion_matrices is not None:
+            mats = [self.confusion_matrices[m].astype('float32').T for m in self.modalities]      # bayes_mix.py:141
+            loglik, logprior = bayes_tables(mats, self.config['class_prior'])
+            self.bayes = (loglik, logprior, torch.from_numpy(loglik).to(self.device), torch.from_numpy(logprior).to(self.device))
+        if self.dirichlet_params is not None:
+            tables = dirichlet_tables([self.dirichlet_params[m] for m in self.modalities], self.class_counts,
+                                      self.config['class_prior'], self.config['sigma'])
+            self.dirichlet = tuple(torch.from_numpy(t).to(self.device) for t in tables)
+
+    def _fusion(self, expert_outputs, output_attr=None):
+        raise UserWarning('ERROR: FusionComparison scores several fusions, it predicts with none: use score_all(), or the '
+                          'fusion model itself')
+
+    # ---- measure both kinds of statistics on one pass ---------------------------------------------------
+    def fit(self, measure_set, *args, **kwargs):
+        """One pass of the experts over `measure_set`: every expert's confusion matrix (what BayesFusion is built from) and
+        the Dirichlet sufficient statistics, then the host fit of DirichletFusion.  Returns {'confusion_matrices': {m: [C,C]},
+        'dirichlet_params': {m: [C,C], 'class_counts': [C]}}."""
+        C = self.config['num_classes']
+        mods = self.modalities
+        cms = {m: torch.zeros((C, C), dtype=torch.int64, device=self.device) for m in mods}
+        S = {m: torch.zeros((C, C), dtype=torch.float64, device=self.device) for m in mods}
+        counts = torch.zeros(C, dtype=torch.int64, device=self.device)
+        scratch = torch.zeros(C, dtype=torch.int64, device=self.device)
+        for batch, labels in _labelled_batches(self, measure_set, None):
+            outs = run_experts(self, batch, ('classification', 'prob'))
+            for i, m in enumerate(mods):
+                ops.confusion_matrix(labels, outs[m]['classification'].contiguous(), cms[m])
+                ops.dirichlet_suffstats(outs[m]['prob'], labels, S[m], counts if i == 0 else scratch)
+        if self.config.get('reduce_score_over_ranks', False):
+            from .parallel import allreduce_sum_
+            allreduce_sum_(*[cms[m] for m in mods])
+            stats, class_counts = DirichletFusion._allreduce_statistics(self, S, counts)
+        else:
+            stats, class_counts = {m: S[m].cpu().numpy() for m in mods}, counts.cpu().numpy()
+        self.sufficient_statistics = (stats, class_counts)
+        self.confusion_matrices = {m: cms[m].cpu().numpy().astype(np.float64) for m in mods}
+        self.dirichlet_params = fit_dirichlet_params(stats, class_counts, self.config['delta'], self.config['beta'], C, mods)
+        self.class_counts = class_counts
+        self._build_tables()
+        params = deepcopy(self.dirichlet_params)
+        params['class_counts'] = self.class_counts
+        return {'confusion_matrices': deepcopy(self.confusion_matrices), 'dirichlet_params': params}
+
+    # ---- score everything on one pass -------------------------------------------------------------------
+    def one_pass_heads_applicable(self):
+        return fused_head_applicable(self) and self.config['num_classes'] <= BayesFusion.JOINT_HIST_MAX_CLASSES
+
+    def score_all(self, test_set, max_iterations=None):
+        """One pass of the experts over `test_set`: {modality: (measures, confusion matrix), ..., 'bayes_fusion': ...,
+        'dirichlet_fusion': ..., 'average_fusion': ...}, each pair what score() of the single model returns."""
+        if self.bayes is None or self.dirichlet is None:
+            raise UserWarning('ERROR: FusionComparison has no measurements yet, call fit() first')
+        C = self.config['num_classes']
+        mods = self.modalities
+        names = list(mods) + list(FUSIONS)
+        am1, lognorm, logprior = self.dirichlet
+        if self.one_pass_heads_applicable():
+            hist = torch.zeros((C, C, C), dtype=torch.int64, device=self.device)
+            counts = torch.zeros((2, C, C), dtype=torch.int64, device=self.device)         # Dirichlet, average
+            tabs = (am1[None].contiguous(), lognorm[None].contiguous(), logprior[None].contiguous())
+            for batch, labels in _labelled_batches(self, test_set, max_iterations):
+                Sa, Sb, ba, bb, n, hi, wi = run_lowres_scores(self, batch)
+                ops.fused_head_joint_hist(Sa, Sb, ba, bb, n, hi, wi, C, labels, hist=hist)
+                ops.fused_head_grid_score(Sa, Sb, ba, bb, n, hi, wi, C, *tabs, labels, cm=counts[0:1])
+                ops.fused_head_average_count(Sa, Sb, ba, bb, n, hi, wi, C, labels, cm=counts[1])
+            self._reduce(hist, counts)
+            hist, counts = hist.cpu().numpy(), counts.cpu().numpy()
+            cm_a, cm_b = expert_matrices_from_joint_hist(hist)
+            bayes = confusion_from_joint_hist(hist, fused_decision_table(self.bayes[0], self.bayes[1]))
+            matrices = [cm_a, cm_b, bayes, counts[0], counts[1]]
+        else:
+            counts = torch.zeros((len(names), C, C), dtype=torch.int64, device=self.device)
+            for batch, labels in _labelled_batches(self, test_set, max_iterations):
+                outs = run_experts(self, batch, ('classification', 'prob'))
+                labs = [outs[m]['classification'].contiguous() for m in mods]
+                probs = [outs[m]['prob'] for m in mods]
+                fused = labs + [ops.bayes_fuse(labs, self.bayes[2], self.bayes[3])[0],
+                                ops.dirichlet_fuse(probs, am1, lognorm, logprior)[0], ops.average_fuse(probs)]
+                for i, pred in enumerate(fused):
+                    ops.confusion_matrix(labels, pred.contiguous(), counts[i])
+            self._reduce(counts)
+            matrices = list(counts.cpu().numpy())
+        out = {}
+        for name, cm in zip(names, matrices):
+            cm = np.asarray(cm).astype(np.float64)
+            out[name] = (score_measures(cm), cm)
+        return out
+
+    def _reduce(self, *tensors):
+        """Sum the counts over the ranks as score() sums its matrix (config reduce_score_over_ranks)."""
+        if self.config.get('reduce_score_over_ranks', False):
+            from .parallel import allreduce_sum_
+            allreduce_sum_(*tensors)

@@ -670,6 +670,38 @@ def fused_head_joint_hist(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels
     return hist
 
 
+def fused_head_average(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, out=None):
+    """Both experts' low-resolution scores -> the average-fused label map (int64 [n, 8hi, 8wi]): the labels of average_fuse on
+    the two probability maps decoder_head_from_scores writes, without those maps."""
+    if out is None:
+        out = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.int64, device=Sa.device)
+    rc = _lib.lib().xv_fused_head_average_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, int(num_classes),
+                                             _ptr(out), _stream())
+    _lib.check(rc, 'xv_fused_head_average_fwd')
+    return out
+
+
+def fused_head_average_count(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, cm=None, max_workgroups=0):
+    """Both experts' low-resolution scores, average-fused and counted against labels (int32 [n, 8hi, 8wi]): accumulates into cm
+    (int64 [C,C], rows = ground truth; made here when None) as confusion_matrix would count fused_head_average's labels, and
+    returns it.  No label map is written."""
+    C = int(num_classes)
+    _check_lowres_pair(Sa, Sb, n, hi, wi, C, labels)
+    _need(bias_a, torch.float32, 'bias_a')
+    _need(bias_b, torch.float32, 'bias_b')
+    if labels.data_ptr() & 15:            # (a slice of a larger map: the kernel reads a pixel group's labels with one load)
+        labels = labels.clone()
+    if cm is None:
+        cm = torch.zeros((C, C), dtype=torch.int64, device=Sa.device)
+    _need(cm, torch.int64, 'cm')
+    if tuple(cm.shape) != (C, C):
+        raise ValueError('cm of shape %s, expected %s' % (tuple(cm.shape), (C, C)))
+    rc = _lib.lib().xv_fused_head_average_count_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C, _ptr(labels),
+                                                   _ptr(cm), int(max_workgroups), _stream())
+    _lib.check(rc, 'xv_fused_head_average_count_fwd')
+    return cm
+
+
 def variance_head(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, num_samples, want_score=False, want_probs=False,
                   want_variance=False):
     """Both experts' low-resolution scores of (num_samples + 1) * n images each (slot 0 plain, then the dropout samples) ->
