@@ -64,6 +64,14 @@ def score_measures(confusion_matrix):
     return measures
 
 
+def reduce_over_ranks(model, *tensors):
+    """Sum device tensors over the ranks, in place, where every rank counted its own shard of the data (config
+    reduce_score_over_ranks: one process per GPU; a few KB each, RCCL all-reduce)."""
+    if model.config.get('reduce_score_over_ranks', False):
+        from .parallel import allreduce_sum_
+        allreduce_sum_(*tensors)
+
+
 class BaseModel(object):
     """Handles IO, batching, scoring and weight files; subclasses implement `_build_graph`
     (create engines / tables) and `_predict_batch`."""
@@ -312,10 +320,7 @@ class BaseModel(object):
         state = {}
         for batch in self._device_batches(iterate_batches(data, self.config['batchsize'], max_iterations), labels=True):
             self._confusion_of_batch(batch, cm_dev, state)
-        if self.config.get('reduce_score_over_ranks', False):
-            # one process per GPU, each scored its own shard: sum the [C,C] counts (RCCL all-reduce)
-            from .parallel import allreduce_sum_
-            allreduce_sum_(cm_dev)
+        reduce_over_ranks(self, cm_dev)
         confusion_matrix = cm_dev.cpu().numpy().astype(np.float64)
         return score_measures(confusion_matrix), confusion_matrix
 

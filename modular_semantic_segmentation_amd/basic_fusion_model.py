@@ -4,7 +4,7 @@ from copy import deepcopy
 import numpy as np
 import torch
 
-from .base_model import BaseModel, iterate_batches, score_measures
+from .base_model import BaseModel, iterate_batches, reduce_over_ranks, score_measures  # noqa: F401
 from .fcn import FcnEngine, init_variables
 
 
@@ -186,22 +186,80 @@ def fused_head_applicable(model):
     return all(isinstance(e, FcnEngine) and e.commuted_head() for e in model.experts.values())
 
 
+def _head_arguments(model, res):
+    """(Sa, Sb, bias_a, bias_b, n, hi, wi), what the two-expert heads take, from {modality: (scores, (n, hi, wi))}."""
+    a, b = model.modalities
+    n, hi, wi = res[a][1]
+    return res[a][0], res[b][0], model.experts[a].b['score'], model.experts[b].b['score'], n, hi, wi
+
+
 def run_lowres_scores(model, batch):
     """Both trunks (run_trunks) up to their low-resolution class scores: (Sa, Sb, bias_a, bias_b, n, hi, wi), what the fused
     heads take."""
     inputs = {m: model._to_device(batch[m], torch.float32) for m in model.modalities}
-    res = run_trunks(model, inputs, lambda m, st: model.experts[m].lowres_scores(inputs[m], st=st))
-    a, b = model.modalities
-    S, geo = {m: r[0] for m, r in res.items()}, res[a][1]
-    return S[a], S[b], model.experts[a].b['score'], model.experts[b].b['score'], geo[0], geo[1], geo[2]
+    return _head_arguments(model, run_trunks(model, inputs, lambda m, st: model.experts[m].lowres_scores(inputs[m], st=st)))
 
 
-def run_fused_head(model, batch, tab, logprior, lognorm=None):
-    """Both trunks (run_trunks) up to their low-resolution class scores, then ONE kernel: per-pixel logits, softmax / argmax
-    per expert and the Bayes or Dirichlet fusion -> fused labels."""
-    from . import ops
-    Sa, Sb, ba, bb, n, hi, wi = run_lowres_scores(model, batch)
-    return ops.fused_head(Sa, Sb, ba, bb, n, hi, wi, model.config['num_classes'], tab, logprior, lognorm=lognorm)
+# ---- MC dropout: what VarianceFusion, UncertaintyMix and BayesianFCN share ---------------------------------------------------
+
+def mc_dropout_setup(name, config, strict=False, fusion=True, engines=()):
+    """Validate the MC-dropout keys of `config` for the model `name` and return (dropout_rate, num_samples, seed of the masks:
+    dropout_seed, else seed, else 0).  A model calls it on its raw config before anything is built -- every refusal that needs
+    no engine comes before a device is touched -- and again with the built `engines`, which must run the commuted decoder
+    head and are given the config's mc_chunk_images (default 64).  strict: a model that divides by the samples' variance
+    needs some (a rate in (0, 1), two samples) where the others take rate 0 and one sample; fusion: the model samples
+    experts, which must be FCNs."""
+    for key in ('dropout_rate', 'num_samples'):
+        if key not in config:
+            raise UserWarning('ERROR: %s needs %s in its config' % (name, key))
+    if fusion and config.get('expert_model', 'fcn') != 'fcn':
+        raise UserWarning('ERROR: %s samples FCN experts only (expert_model=%r)' % (name, config['expert_model']))
+    rate, T = float(config['dropout_rate']), int(config['num_samples'])
+    if strict:
+        if not 0.0 < rate < 1.0:
+            raise ValueError('dropout_rate must lie in (0, 1): without dropout there is no variance to weigh the experts by')
+        if T < 2:
+            raise ValueError('num_samples must be at least 2: one sample has no variance')
+    elif not 0.0 <= rate < 1.0 or T < 1:
+        raise ValueError('dropout_rate must lie in [0, 1) and num_samples be at least 1')
+    for e in engines:
+        if not e.commuted_head():
+            raise NotImplementedError('%s needs experts with the commuted decoder head (bilinear x8 deconv)' % name)
+        e.mc_chunk_images = int(config.get('mc_chunk_images', 64))
+    seed = config.get('dropout_seed', config.get('seed'))
+    return rate, T, int(seed) if seed is not None else 0
+
+
+def run_mc_lowres_scores(model, batch, sampler):
+    """run_lowres_scores of an MC-dropout fusion: the engine method named `sampler` ('mc_lowres_scores', 'mc_input_scores')
+    gives each expert's plain pass and its num_samples dropped passes as one slot-major score tensor, every expert under
+    masks of its own (seed + its index).  Every call draws new masks: such a model never captures its step (_graph_capturable)."""
+    inputs = {m: model._to_device(batch[m], torch.float32) for m in model.modalities}
+    rate, T = float(model.config['dropout_rate']), int(model.config['num_samples'])
+    seeds = {m: model._dropout_seed + i for i, m in enumerate(model.modalities)}
+    # pair=False: the samplers run their own trunks -- a paired section would skip the replication at the dropout site
+    return _head_arguments(model, run_trunks(
+        model, inputs, lambda m, st: getattr(model.experts[m], sampler)(inputs[m], T, rate, seeds[m]), pair=False))
+
+
+def per_expert_output(model, t, keep=None):
+    """An optional output of a two-expert head, [E, N, ...], as predict returns it: [N, E, ...]; keep: the attribute that
+    holds {modality: its slice} afterwards (`probs`, `variances`)."""
+    if keep is not None:
+        setattr(model, keep, {m: t[i] for i, m in enumerate(model.modalities)})
+    return t.transpose(0, 1).contiguous()
+
+
+# ---- small change shared by the *_mix modules --------------------------------------------------------------------------------
+
+def device_tables(device, *tables):
+    """The numpy tables of a fusion (bayes_tables, dirichlet_tables, ...) as device tensors, in order."""
+    return tuple(torch.from_numpy(t).to(device) for t in tables)
+
+
+def output_key(output_attr):
+    """The one name of an optional output: 'score' is 'fused_score', 'prob' is 'probs'; anything else is itself."""
+    return {'score': 'fused_score', 'prob': 'probs'}.get(output_attr, output_attr)
 
 
 # ---- grid search over the fusion parameters in ONE pass of the experts (experiments/different_evaluation_parameters.py) ------
@@ -256,12 +314,25 @@ def score_grid_generic(model, data, num_points, wants, fuse_point, max_iteration
     return counts
 
 
-def reduce_grid_counts(model, counts):
-    """Sum the counts over the ranks as score() sums its matrix (config reduce_score_over_ranks)."""
-    if model.config.get('reduce_score_over_ranks', False):
-        from .parallel import allreduce_sum_
-        allreduce_sum_(counts)
-    return counts
+def measure_experts(model, data, confusion=False):
+    """One pass of the experts over the labelled batches of `data` (dirichlet_mix.py:175-205): per modality the Dirichlet
+    sufficient statistics S[c,k] = sum_{label=c} log(1e-10 + p[k]) (float64 [C,C]), the class counts (int64 [C]) and, with
+    confusion=True, every expert's confusion matrix (int64 [C,C], rows = ground truth).  Returns (S, counts, matrices or None)
+    on the device, this rank's share: the caller sums over ranks."""
+    from . import ops
+    C, mods = model.config['num_classes'], model.modalities
+    S = {m: torch.zeros((C, C), dtype=torch.float64, device=model.device) for m in mods}
+    cms = {m: torch.zeros((C, C), dtype=torch.int64, device=model.device) for m in mods} if confusion else None
+    counts = torch.zeros(C, dtype=torch.int64, device=model.device)
+    scratch = torch.zeros(C, dtype=torch.int64, device=model.device)     # every expert sees the same labels: count them once
+    wants = ('classification', 'prob') if confusion else ('prob',)
+    for batch, labels in _labelled_batches(model, data, None):
+        outs = run_experts(model, batch, wants)
+        for i, m in enumerate(mods):
+            if confusion:
+                ops.confusion_matrix(labels, outs[m]['classification'].contiguous(), cms[m])
+            ops.dirichlet_suffstats(outs[m]['prob'], labels, S[m], counts if i == 0 else scratch)
+    return S, counts, cms
 
 
 def grid_results(configs, confusion_matrices):
@@ -274,29 +345,42 @@ def grid_results(configs, confusion_matrices):
 
 
 class FusionModel(BaseModel):
-    """Mixture of per-modality FCN experts; subclasses implement `_fusion(expert_outputs)`.
-    config: prefixes {modality: prefix}, num_units, num_channels {modality: C_in}, expert_model."""
+    """Mixture of per-modality experts, which this class builds and owns; subclasses implement `_fusion(expert_outputs)` and
+    may name a fused head.  config: prefixes {modality: prefix} or modalities (a list: every expert's prefix is its modality,
+    dirichlet_mix.py:98), num_units, num_channels {modality: C_in}, expert_model."""
 
     expert_wants = ('classification',)
 
     def __init__(self, name=None, output_dir=None, **config):
-        self.modalities = list(config['prefixes'].keys())
+        self.modalities = list(config['prefixes'] if 'prefixes' in config else config['modalities'])
         BaseModel.__init__(self, name=name, output_dir=output_dir, custom_training=True, **config)
 
     def _fusion(self, expert_outputs, output_attr=None):
         raise NotImplementedError
 
-    def _build_graph(self):
+    def _fused_head(self):
+        """The model's head for both experts' low-resolution scores -- head(Sa, Sb, bias_a, bias_b, n, hi, wi) -> fused
+        labels in ONE kernel, per-expert softmax / argmax included -- or None: it fuses materialised expert outputs only."""
+        return None
+
+    def _build_experts(self):
+        """Hook: fills self.experts {modality: engine} and self.variables (a test without a GPU overrides it)."""
         engine_cls, init = expert_factory(self.config['expert_model'], self.config.get('conv_dtype', 'bf16'))
         self.experts = {}
         for m in self.modalities:
-            prefix = self.config['prefixes'][m]
+            prefix = self.config['prefixes'][m] if 'prefixes' in self.config else m
             cin = self._modality_channels(m)
             # experts run with trainable=False, batchnorm=False (basic_fusion_model.py:17-18)
             self.variables.update(init(prefix, cin, self.config['num_units'], self.config['num_classes'],
                                        seed=self.config.get('seed')))
             self.experts[m] = engine_cls(prefix, cin, self.config['num_units'], self.config['num_classes'],
                                          self.variables, device=self.device, **engine_options(self.config))
+
+    def _build_graph(self):
+        # ONCE per model object: a model that refits its tables calls _initialize_graph() again (DirichletFusion.fit), and a
+        # second build would re-draw the variables and discard imported weights
+        if not hasattr(self, 'experts'):
+            self._build_experts()
         self.prediction = 'fused_label'
 
     def _modality_channels(self, m):
@@ -312,12 +396,16 @@ class FusionModel(BaseModel):
     def calibrate(self, data):
         return calibrate_experts(self, data)
 
-    def _expert_outputs(self, batch, wants):
-        return run_experts(self, batch, wants)
-
     def _predict_batch_impl(self, batch, output_attr=None):
+        head = self._fused_head() if output_attr is None else None
+        if head is not None and fused_head_applicable(self):
+            # default prediction: nothing but the fused label map is wanted -> one head kernel after the trunks; the experts'
+            # labels and probabilities never leave its registers
+            self.expert_outputs = None
+            return head(*run_lowres_scores(self, batch))
+        key = output_key(output_attr)
         wants = self.expert_wants
-        if output_attr in ('probs', 'prob') and 'prob' not in wants:
+        if key == 'probs' and 'prob' not in wants:
             wants = tuple(wants) + ('prob',)
-        self.expert_outputs = self._expert_outputs(batch, wants)
-        return self._fusion(self.expert_outputs, output_attr=output_attr)
+        self.expert_outputs = run_experts(self, batch, wants)
+        return self._fusion(self.expert_outputs, output_attr=key)

@@ -5,8 +5,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .basic_fusion_model import (FusionModel, fused_head_applicable, grid_point_configs, grid_results, reduce_grid_counts,
-                                 run_fused_head, score_grid_fused, score_grid_generic)
+from .basic_fusion_model import (FusionModel, device_tables, fused_head_applicable, grid_point_configs, grid_results,
+                                 reduce_over_ranks, score_grid_fused, score_grid_generic)
 
 UNIFORM_PRIOR = 1.0 / 14     # the reference hard-codes 1/14 regardless of num_classes (bayes_mix.py:42,95)
 
@@ -48,9 +48,8 @@ def bayes_fusion(classifications, confusion_matrices, class_prior='data'):
     Returns (score f32 [N,H,W,C], log_likelihoods, conditionals); the per-expert lists hold the
     [C,C] tables the per-pixel gathers of the reference index into."""
     loglik, logprior = bayes_tables(confusion_matrices, class_prior)
-    dev = classifications[0].device
-    _, score = ops.bayes_fuse(list(classifications), torch.from_numpy(loglik).to(dev),
-                              torch.from_numpy(logprior).to(dev), want_score=True)
+    _, score = ops.bayes_fuse(list(classifications), *device_tables(classifications[0].device, loglik, logprior),
+                              want_score=True)
     return score, [l for l in loglik], [_conditional(m) for m in confusion_matrices]
 
 
@@ -114,23 +113,19 @@ class BayesFusion(FusionModel):
         # modality order = order of the confusion_matrices dict (bayes_mix.py:137-141 overwrites
         # self.modalities before FusionModel.__init__ resets it from `prefixes`)
         mats = [self.confusion_matrices[m] for m in self.modalities]
-        loglik, logprior = bayes_tables(mats, self.config['class_prior'])
-        self.loglik = torch.from_numpy(loglik).to(self.device)
-        self.logprior = torch.from_numpy(logprior).to(self.device)
+        self.loglik, self.logprior = device_tables(self.device, *bayes_tables(mats, self.config['class_prior']))
         self.conditionals = [_conditional(m) for m in mats]
-        self.decision_matrix = torch.from_numpy(
-            bayes_decision_matrix(mats, self.config['class_prior']).astype(np.int64)).to(self.device)
+        lut = bayes_decision_matrix(mats, self.config['class_prior']).astype(np.int64)
+        self.decision_matrix = device_tables(self.device, lut)[0]
 
-    def _predict_batch_impl(self, batch, output_attr=None):
-        if output_attr is None and not self.config.get('decision_matrix', False) and fused_head_applicable(self):
-            # default prediction: nothing but the fused label map is wanted -> one fused head kernel after the trunks
-            self.expert_outputs = None
-            return run_fused_head(self, batch, self.loglik, self.logprior)
-        return FusionModel._predict_batch_impl(self, batch, output_attr)
+    def _fused_head(self):
+        if self.config.get('decision_matrix', False):
+            return None             # the lookup table takes the experts' materialised label maps
+        return lambda *scores: ops.fused_head(*scores, self.config['num_classes'], self.loglik, self.logprior)
 
     def _fusion(self, expert_outputs, output_attr=None):
         labels = [expert_outputs[m]['classification'] for m in self.modalities]
-        want_score = output_attr in ('fused_score', 'score')
+        want_score = output_attr == 'fused_score'
         if self.config.get('decision_matrix', False) and len(labels) == 2 and not want_score:
             self.probs = {m: expert_outputs[m].get('prob') for m in self.modalities}
             return ops.bayes_fuse_lut(labels[0], labels[1], self.decision_matrix)
@@ -138,7 +133,7 @@ class BayesFusion(FusionModel):
         self.probs = {m: expert_outputs[m].get('prob') for m in self.modalities}
         if want_score:
             return score
-        if output_attr in ('probs', 'prob'):
+        if output_attr == 'probs':
             return torch.stack([self.probs[m] for m in self.modalities], 1)
         return fused
 
@@ -161,20 +156,21 @@ class BayesFusion(FusionModel):
             def count_batch(Sa, Sb, ba, bb, n, hi, wi, labels, hist):
                 ops.fused_head_joint_hist(Sa, Sb, ba, bb, n, hi, wi, C, labels, hist=hist)
             score_grid_fused(self, data, hist, count_batch, max_iterations)
-            hist = reduce_grid_counts(self, hist).cpu().numpy()
+            reduce_over_ranks(self, hist)
+            hist = hist.cpu().numpy()
             counts = [confusion_from_joint_hist(hist, fused_decision_table(*bayes_tables(mats, c['class_prior'])))
                       for c in configs]
             return grid_results(configs, counts)
         if lut and len(self.modalities) == 2:
-            luts = [torch.from_numpy(bayes_decision_matrix(mats, c['class_prior']).astype(np.int64)).to(self.device)
-                    for c in configs]
+            luts = device_tables(self.device, *[bayes_decision_matrix(mats, c['class_prior']).astype(np.int64) for c in configs])
 
             def fuse_point(outs, g):
                 return ops.bayes_fuse_lut(*[outs[m]['classification'] for m in self.modalities], luts[g])
         else:
-            tables = [tuple(torch.from_numpy(t).to(self.device) for t in bayes_tables(mats, c['class_prior'])) for c in configs]
+            tables = [device_tables(self.device, *bayes_tables(mats, c['class_prior'])) for c in configs]
 
             def fuse_point(outs, g):
                 return ops.bayes_fuse([outs[m]['classification'] for m in self.modalities], *tables[g])[0]
         counts = score_grid_generic(self, data, len(configs), ('classification',), fuse_point, max_iterations)
-        return grid_results(configs, reduce_grid_counts(self, counts).cpu().numpy())
+        reduce_over_ranks(self, counts)
+        return grid_results(configs, counts.cpu().numpy())

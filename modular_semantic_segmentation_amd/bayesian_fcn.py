@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from .base_model import iterate_batches
+from .basic_fusion_model import mc_dropout_setup
 from .simple_fcn import SimpleFCN
 from .uncertainty_model import UncertaintyModel
 
@@ -67,9 +68,7 @@ class BayesianFCN(UncertaintyModel, SimpleFCN):
 
     def __init__(self, prefix, data_description, modality, output_dir=None,
                  dropout_layers=['pool3', 'pool4', 'conv4_3', 'conv5_3', 'features'], **config):
-        for key in ('dropout_rate', 'num_samples'):
-            if key not in config:
-                raise UserWarning('ERROR: BayesianFCN needs %s in its config' % key)
+        mc_dropout_setup('BayesianFCN', config, fusion=False)
         standard_config = {'method': 'sampling', 'batch_normalization': False, 'learning_rate': 0.0}
         standard_config.update(config)
         if standard_config['method'] != 'sampling':
@@ -83,12 +82,7 @@ class BayesianFCN(UncertaintyModel, SimpleFCN):
                                       'no batch norm shift before its relu): batch_normalization=True and the fp8 / fp32 '
                                       'engines are not sampled')
         SimpleFCN._build_graph(self)
-        rate, T = float(self.config['dropout_rate']), int(self.config['num_samples'])
-        if not 0.0 <= rate < 1.0 or T < 1:
-            raise ValueError('dropout_rate must lie in [0, 1) and num_samples be at least 1')
-        self.engine.mc_chunk_images = int(self.config.get('mc_chunk_images', 64))
-        seed = self.config.get('dropout_seed', self.config.get('seed'))
-        self._dropout_seed = int(seed) if seed is not None else 0
+        self._dropout_seed = mc_dropout_setup('BayesianFCN', self.config, fusion=False, engines=[self.engine])[2]
 
     def _graph_capturable(self):
         return False

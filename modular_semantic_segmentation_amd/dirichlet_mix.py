@@ -6,10 +6,9 @@ import torch
 from scipy.special import gammaln
 
 from . import ops
-from .base_model import BaseModel, iterate_batches
-from .basic_fusion_model import (calibrate_experts, engine_options, expert_factory, fused_head_applicable,  # noqa: F401
-                                 grid_point_configs, grid_results, reduce_grid_counts, run_experts, run_fused_head,
-                                 score_grid_fused, score_grid_generic, test_pipeline)
+from .basic_fusion_model import (FusionModel, calibrate_experts, device_tables, engine_options, expert_factory,  # noqa: F401
+                                 fused_head_applicable, grid_point_configs, grid_results, measure_experts, reduce_over_ranks,
+                                 run_experts, score_grid_fused, score_grid_generic, test_pipeline)
 from .dirichlet_fit import find_dirichlet_priors
 
 UNIFORM_PRIOR = 1.0 / 14     # dirichlet_mix.py:116
@@ -53,9 +52,7 @@ def dirichlet_fusion(probs, dirichlet_params, prior, sigma=1.0):
     [C,C] arrays (params[k, c]), prior = [C] probabilities.  Returns the fused score [N,H,W,C]."""
     am1, lognorm, _ = dirichlet_tables(dirichlet_params, np.ones(len(prior)), 'uniform', sigma)
     logprior = np.log(np.float32(1e-20) + np.asarray(prior, np.float32), dtype=np.float32)
-    dev = probs[0].device
-    _, score = ops.dirichlet_fuse(list(probs), torch.from_numpy(am1).to(dev), torch.from_numpy(lognorm).to(dev),
-                                  torch.from_numpy(logprior).to(dev), want_score=True)
+    _, score = ops.dirichlet_fuse(list(probs), *device_tables(probs[0].device, am1, lognorm, logprior), want_score=True)
     return score
 
 
@@ -79,90 +76,57 @@ def fit_dirichlet_params(counts, class_counts, delta, beta, num_classes, modalit
     return {m: dirichlet_em(counts[m]) for m in modalities}
 
 
-class DirichletFusion(BaseModel):
+class DirichletFusion(FusionModel):
     """config: modalities, num_channels, num_units, expert_model, class_prior, sigma, delta, beta,
     optional dirichlet_params {modality: [C,C], 'class_counts': [C]}; the expert of modality m uses
     prefix m (dirichlet_mix.py:98)."""
 
+    expert_wants = ('prob',)
+
     def __init__(self, output_dir=None, **config):
         standard_config = {'learning_rate': 0.0}
         standard_config.update(config)
-        self.modalities = config['modalities']
         if 'dirichlet_params' in config:
             measurements = config['dirichlet_params']
-            self.dirichlet_params = {m: np.asarray(measurements[m]).astype('float32') for m in self.modalities}
+            self.dirichlet_params = {m: np.asarray(measurements[m]).astype('float32') for m in config['modalities']}
             self.class_counts = np.asarray(measurements['class_counts']).astype('float32')
         else:
             print('WARNING: Could not yet import measurements, you need to fit this model first.')
-        BaseModel.__init__(self, name='DirichletFusion', output_dir=output_dir, custom_training=True,
-                           **standard_config)
-
-    def _build_experts(self):
-        engine_cls, init = expert_factory(self.config['expert_model'], self.config.get('conv_dtype', 'bf16'))
-        if not hasattr(self, 'experts'):
-            self.experts = {}
-            for m in self.modalities:
-                cin = int(self.config['num_channels'][m])
-                self.variables.update(init(m, cin, self.config['num_units'], self.config['num_classes'],
-                                           seed=self.config.get('seed')))
-                self.experts[m] = engine_cls(m, cin, self.config['num_units'], self.config['num_classes'],
-                                             self.variables, device=self.device, **engine_options(self.config))
+        FusionModel.__init__(self, name='DirichletFusion', output_dir=output_dir, **standard_config)
 
     def _build_graph(self):
-        self._build_experts()
+        FusionModel._build_graph(self)
         if hasattr(self, 'dirichlet_params'):
-            am1, lognorm, logprior = dirichlet_tables([self.dirichlet_params[m] for m in self.modalities],
-                                                      self.class_counts, self.config['class_prior'],
-                                                      self.config['sigma'])
-            self.am1 = torch.from_numpy(am1).to(self.device)
-            self.lognorm = torch.from_numpy(lognorm).to(self.device)
-            self.logprior = torch.from_numpy(logprior).to(self.device)
-            self.prediction = 'fused_label'
+            self.am1, self.lognorm, self.logprior = device_tables(self.device, *dirichlet_tables(
+                [self.dirichlet_params[m] for m in self.modalities], self.class_counts, self.config['class_prior'],
+                self.config['sigma']))
         else:
             self.prediction = 0      # dirichlet_mix.py:165-168: no fusion possible before fit()
-
-    def _variables_changed(self):
-        BaseModel._variables_changed(self)
-        for m in self.modalities:
-            self.experts[m].load(self.variables)
-
-    def calibrate(self, data):
-        return calibrate_experts(self, data)
 
     def _predict_batch_impl(self, batch, output_attr=None):
         if not hasattr(self, 'am1'):
             raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
-        if output_attr is None and fused_head_applicable(self):
-            # default prediction: the experts' probabilities never leave the registers of the fused head kernel
-            self.probs = None
-            return run_fused_head(self, batch, self.am1, self.logprior, lognorm=self.lognorm)
-        outs = run_experts(self, batch, ('prob',))
-        probs = [outs[m]['prob'] for m in self.modalities]
+        self.probs = None       # (stays so on the fused route: the probabilities never leave the head's registers)
+        return FusionModel._predict_batch_impl(self, batch, output_attr)
+
+    def _fused_head(self):
+        return lambda *scores: ops.fused_head(*scores, self.config['num_classes'], self.am1, self.logprior, lognorm=self.lognorm)
+
+    def _fusion(self, expert_outputs, output_attr=None):
+        probs = [expert_outputs[m]['prob'] for m in self.modalities]
         self.probs = dict(zip(self.modalities, probs))
-        want_score = output_attr in ('fused_score', 'score')
+        want_score = output_attr == 'fused_score'
         fused, score = ops.dirichlet_fuse(probs, self.am1, self.lognorm, self.logprior, want_score=want_score)
         return score if want_score else fused
 
     # ---- fit = measure sufficient statistics on the GPU, Newton-fit on the host -------------------
     def _get_sufficient_statistic(self, data):
-        """dirichlet_mix.py:175-205: per modality S[c,k] = sum_{label=c} log(1e-10 + p[k]) and the
-        class counts, accumulated over all batches (float64 / int64 on the device)."""
-        C = self.config['num_classes']
-        S = {m: torch.zeros((C, C), dtype=torch.float64, device=self.device) for m in self.modalities}
-        counts = torch.zeros(C, dtype=torch.int64, device=self.device)
-        scratch = torch.zeros(C, dtype=torch.int64, device=self.device)
-        for batch in self._device_batches(iterate_batches(data, self.config['batchsize']), labels=True):
-            labels = self._to_device(batch['labels'], torch.int32)
-            outs = run_experts(self, batch, ('prob',))
-            for i, m in enumerate(self.modalities):
-                ops.dirichlet_suffstats(outs[m]['prob'], labels, S[m], counts if i == 0 else scratch)
-        return self._allreduce_statistics({m: S[m] for m in self.modalities}, counts)
-
-    def _allreduce_statistics(self, S, counts):
-        """Sum the per-rank statistics when running one process per GPU (each rank measured its
-        shard of the data): one tiny all-reduce per tensor, RCCL over xGMI."""
+        """measure_experts over `data`, summed over the ranks (one process per GPU, each measured its shard of the data: one
+        tiny all-reduce per tensor, RCCL over xGMI) whatever reduce_score_over_ranks says: ({modality: float64 [C,C]},
+        int64 [C]) on the host."""
         from .parallel import allreduce_sum_
-        allreduce_sum_(counts, *[S[m] for m in S])
+        S, counts, _ = measure_experts(self, data)
+        allreduce_sum_(counts, *S.values())
         return {m: S[m].cpu().numpy() for m in S}, counts.cpu().numpy()
 
     def _fit_sufficient_statistic(self, counts, class_counts):
@@ -214,7 +178,7 @@ class DirichletFusion(BaseModel):
         configs = grid_point_configs(self, search_parameters, self.searchable)
         if not hasattr(self, 'dirichlet_params') and not hasattr(self, 'sufficient_statistics'):
             raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
-        tables = [tuple(torch.from_numpy(t).to(self.device) for t in point) for point in self._grid_tables(configs)]
+        tables = [device_tables(self.device, *point) for point in self._grid_tables(configs)]
         C = self.config['num_classes']
         if fused_head_applicable(self):
             am1, lognorm, logprior = (torch.stack([point[i] for point in tables]).contiguous() for i in range(3))
@@ -227,4 +191,5 @@ class DirichletFusion(BaseModel):
             def fuse_point(outs, g):
                 return ops.dirichlet_fuse([outs[m]['prob'] for m in self.modalities], *tables[g])[0]
             counts = score_grid_generic(self, data, len(configs), ('prob',), fuse_point, max_iterations)
-        return grid_results(configs, reduce_grid_counts(self, counts).cpu().numpy())
+        reduce_over_ranks(self, counts)
+        return grid_results(configs, counts.cpu().numpy())

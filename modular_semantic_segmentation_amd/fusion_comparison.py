@@ -16,9 +16,10 @@ import torch
 
 from . import ops
 from .base_model import score_measures
-from .basic_fusion_model import FusionModel, _labelled_batches, fused_head_applicable, run_experts, run_lowres_scores
+from .basic_fusion_model import (FusionModel, _labelled_batches, device_tables, fused_head_applicable, measure_experts,
+                                 reduce_over_ranks, run_experts, run_lowres_scores)
 from .bayes_mix import BayesFusion, bayes_tables, confusion_from_joint_hist, fused_decision_table
-from .dirichlet_mix import DirichletFusion, dirichlet_tables, fit_dirichlet_params
+from .dirichlet_mix import dirichlet_tables, fit_dirichlet_params
 
 FUSIONS = ('bayes_fusion', 'dirichlet_fusion', 'average_fusion')
 
@@ -59,11 +60,11 @@ class FusionComparison(FusionModel):
         if self.confusion_matrices is not None:
             mats = [self.confusion_matrices[m].astype('float32').T for m in self.modalities]      # bayes_mix.py:141
             loglik, logprior = bayes_tables(mats, self.config['class_prior'])
-            self.bayes = (loglik, logprior, torch.from_numpy(loglik).to(self.device), torch.from_numpy(logprior).to(self.device))
+            self.bayes = (loglik, logprior) + device_tables(self.device, loglik, logprior)
         if self.dirichlet_params is not None:
-            tables = dirichlet_tables([self.dirichlet_params[m] for m in self.modalities], self.class_counts,
-                                      self.config['class_prior'], self.config['sigma'])
-            self.dirichlet = tuple(torch.from_numpy(t).to(self.device) for t in tables)
+            self.dirichlet = device_tables(self.device, *dirichlet_tables(
+                [self.dirichlet_params[m] for m in self.modalities], self.class_counts, self.config['class_prior'],
+                self.config['sigma']))
 
     def _fusion(self, expert_outputs, output_attr=None):
         raise UserWarning('ERROR: FusionComparison scores several fusions, it predicts with none: use score_all(), or the '
@@ -76,21 +77,9 @@ class FusionComparison(FusionModel):
         'dirichlet_params': {m: [C,C], 'class_counts': [C]}}."""
         C = self.config['num_classes']
         mods = self.modalities
-        cms = {m: torch.zeros((C, C), dtype=torch.int64, device=self.device) for m in mods}
-        S = {m: torch.zeros((C, C), dtype=torch.float64, device=self.device) for m in mods}
-        counts = torch.zeros(C, dtype=torch.int64, device=self.device)
-        scratch = torch.zeros(C, dtype=torch.int64, device=self.device)
-        for batch, labels in _labelled_batches(self, measure_set, None):
-            outs = run_experts(self, batch, ('classification', 'prob'))
-            for i, m in enumerate(mods):
-                ops.confusion_matrix(labels, outs[m]['classification'].contiguous(), cms[m])
-                ops.dirichlet_suffstats(outs[m]['prob'], labels, S[m], counts if i == 0 else scratch)
-        if self.config.get('reduce_score_over_ranks', False):
-            from .parallel import allreduce_sum_
-            allreduce_sum_(*[cms[m] for m in mods])
-            stats, class_counts = DirichletFusion._allreduce_statistics(self, S, counts)
-        else:
-            stats, class_counts = {m: S[m].cpu().numpy() for m in mods}, counts.cpu().numpy()
+        S, counts, cms = measure_experts(self, measure_set, confusion=True)
+        reduce_over_ranks(self, *cms.values(), counts, *S.values())
+        stats, class_counts = {m: S[m].cpu().numpy() for m in mods}, counts.cpu().numpy()
         self.sufficient_statistics = (stats, class_counts)
         self.confusion_matrices = {m: cms[m].cpu().numpy().astype(np.float64) for m in mods}
         self.dirichlet_params = fit_dirichlet_params(stats, class_counts, self.config['delta'], self.config['beta'], C, mods)
@@ -122,7 +111,7 @@ class FusionComparison(FusionModel):
                 ops.fused_head_joint_hist(Sa, Sb, ba, bb, n, hi, wi, C, labels, hist=hist)
                 ops.fused_head_grid_score(Sa, Sb, ba, bb, n, hi, wi, C, *tabs, labels, cm=counts[0:1])
                 ops.fused_head_average_count(Sa, Sb, ba, bb, n, hi, wi, C, labels, cm=counts[1])
-            self._reduce(hist, counts)
+            reduce_over_ranks(self, hist, counts)
             hist, counts = hist.cpu().numpy(), counts.cpu().numpy()
             cm_a, cm_b = expert_matrices_from_joint_hist(hist)
             bayes = confusion_from_joint_hist(hist, fused_decision_table(self.bayes[0], self.bayes[1]))
@@ -137,16 +126,10 @@ class FusionComparison(FusionModel):
                                 ops.dirichlet_fuse(probs, am1, lognorm, logprior)[0], ops.average_fuse(probs)]
                 for i, pred in enumerate(fused):
                     ops.confusion_matrix(labels, pred.contiguous(), counts[i])
-            self._reduce(counts)
+            reduce_over_ranks(self, counts)
             matrices = list(counts.cpu().numpy())
         out = {}
         for name, cm in zip(names, matrices):
             cm = np.asarray(cm).astype(np.float64)
             out[name] = (score_measures(cm), cm)
         return out
-
-    def _reduce(self, *tensors):
-        """Sum the counts over the ranks as score() sums its matrix (config reduce_score_over_ranks)."""
-        if self.config.get('reduce_score_over_ranks', False):
-            from .parallel import allreduce_sum_
-            allreduce_sum_(*tensors)

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .basic_fusion_model import run_trunks
+from .basic_fusion_model import FusionModel, device_tables, mc_dropout_setup, per_expert_output, run_mc_lowres_scores
 from .dirichlet_mix import DirichletFusion, class_prior_vector
 
 
@@ -36,7 +36,7 @@ def _tables(conditional_params, prior, device):
     C = params.shape[1]
     prior = np.broadcast_to(np.asarray(prior, np.float32), (C,))
     logprior = np.log(np.float32(1e-20) + prior, dtype=np.float32)
-    return torch.from_numpy(params).to(device), torch.from_numpy(np.ascontiguousarray(logprior)).to(device)
+    return device_tables(device, params, np.ascontiguousarray(logprior))
 
 
 def dirichlet_uncertainty_fusion(probs, conditional_params, uncertainties, prior):
@@ -71,16 +71,7 @@ class UncertaintyMix(DirichletFusion):
     step is never captured into a hipGraph: a replay would redraw the masks of the captured call."""
 
     def __init__(self, output_dir=None, **config):
-        for key in ('dropout_rate', 'num_samples'):
-            if key not in config:
-                raise UserWarning('ERROR: UncertaintyMix needs %s in its config' % key)
-        if config.get('expert_model', 'fcn') != 'fcn':
-            raise UserWarning('ERROR: UncertaintyMix samples FCN experts only (expert_model=%r)' % config['expert_model'])
-        rate, T = float(config['dropout_rate']), int(config['num_samples'])
-        if not 0.0 < rate < 1.0:
-            raise ValueError('dropout_rate must lie in (0, 1): without dropout there is no variance to weigh the experts by')
-        if T < 2:
-            raise ValueError('num_samples must be at least 2: one sample has no variance')
+        mc_dropout_setup('UncertaintyMix', config, strict=True)
         if len(config['modalities']) != 2:
             raise UserWarning('ERROR: UncertaintyMix fuses two experts, got %d' % len(config['modalities']))
         if config.get('conv_dtype', 'bf16') != 'bf16':
@@ -90,18 +81,12 @@ class UncertaintyMix(DirichletFusion):
         self.name = 'UncertaintyMix'
 
     def _build_graph(self):
-        self._build_experts()
-        for e in self.experts.values():
-            if not e.commuted_head():
-                raise NotImplementedError('UncertaintyMix needs experts with the commuted decoder head (bilinear x8 deconv)')
-            e.mc_chunk_images = int(self.config.get('mc_chunk_images', 64))
-        seed = self.config.get('dropout_seed', self.config.get('seed'))
-        self._dropout_seed = int(seed) if seed is not None else 0
+        FusionModel._build_graph(self)
+        self._dropout_seed = mc_dropout_setup('UncertaintyMix', self.config, strict=True, engines=self.experts.values())[2]
         if hasattr(self, 'dirichlet_params'):
             C = self.config['num_classes']
             prior = class_prior_vector(self.class_counts, self.config['class_prior'], C)
             self.params_dev, self.logprior = _tables([self.dirichlet_params[m] for m in self.modalities], prior, self.device)
-            self.prediction = 'fused_label'
         else:
             self.prediction = 0      # no fusion possible before fit()
 
@@ -114,24 +99,13 @@ class UncertaintyMix(DirichletFusion):
         key = 'label' if output_attr is None else output_attr
         if key not in ('label', 'fused_score', 'probs', 'variance', 'mix'):
             raise UserWarning('ERROR: UncertaintyMix has no output %r' % output_attr)
-        inputs = {m: self._to_device(batch[m], torch.float32) for m in self.modalities}
-        rate, T = float(self.config['dropout_rate']), int(self.config['num_samples'])
-        seeds = {m: self._dropout_seed + i for i, m in enumerate(self.modalities)}     # independent masks per expert
-        res = run_trunks(self, inputs, lambda m, st: self.experts[m].mc_input_scores(inputs[m], T, rate, seeds[m]), pair=False)
-        a, b = self.modalities
-        n, hi, wi = res[a][1]
-        bias = (self.experts[a].b['score'], self.experts[b].b['score'])
+        scores = run_mc_lowres_scores(self, batch, 'mc_input_scores')
         C = self.config['num_classes']
-        mvar, vmax = ops.uncertainty_moments(res[a][0], res[b][0], bias[0], bias[1], n, hi, wi, C, T)
+        mvar, vmax = ops.uncertainty_moments(*scores, C, int(self.config['num_samples']))
         if key == 'variance':
-            self.variances = {m: mvar[i] for i, m in enumerate(self.modalities)}
-            return mvar.transpose(0, 1).contiguous()
-        out = ops.uncertainty_dirichlet_head(res[a][0], res[b][0], bias[0], bias[1], n, hi, wi, C, mvar, vmax, self.params_dev,
-                                             self.logprior, want_score=key == 'fused_score', want_probs=key == 'probs',
-                                             want_mix=key == 'mix')
-        if key == 'probs':
-            self.probs = {m: out['probs'][i] for i, m in enumerate(self.modalities)}
-            return out['probs'].transpose(0, 1).contiguous()
-        if key == 'mix':
-            return out['mix'].transpose(0, 1).contiguous()
+            return per_expert_output(self, mvar, keep='variances')
+        out = ops.uncertainty_dirichlet_head(*scores, C, mvar, vmax, self.params_dev, self.logprior,
+                                             want_score=key == 'fused_score', want_probs=key == 'probs', want_mix=key == 'mix')
+        if key in ('probs', 'mix'):
+            return per_expert_output(self, out[key], keep='probs' if key == 'probs' else None)
         return out[key]

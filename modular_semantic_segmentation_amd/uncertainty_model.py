@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .base_model import iterate_batches
+from .base_model import iterate_batches, reduce_over_ranks
 
 METRICS = ops.UNCERTAINTY_METRICS
 
@@ -162,9 +162,7 @@ class UncertaintyModel(object):
                 self._uncertainty_accumulate(state, labels, tables, t, fixed_row)
 
     def _finish(self, tables):
-        if self.config.get('reduce_score_over_ranks', False):
-            from .parallel import allreduce_sum_
-            allreduce_sum_(tables['hist'], tables['nll'], tables['counts'])
+        reduce_over_ranks(self, tables['hist'], tables['nll'], tables['counts'])
         m, o = self._uncertainty_bins()
         return {'metrics': tuple(self.uncertainty_metrics), 'hist': tables['hist'].cpu().numpy(),
                 'nll_sum': tables['nll'].cpu().numpy(), 'counts': tables['counts'].cpu().numpy(), 'edges': bin_edges(m, o)}

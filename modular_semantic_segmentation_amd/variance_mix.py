@@ -5,10 +5,8 @@ pass without; the variance of the samples' softmax over the samples, averaged ov
 probabilities: fused = sum_m prob_m / (1e-20 + var_m) / sum_m 1 / (1e-20 + var_m), label = argmax(fused).  Here the layers
 before the first dropout site run once per expert, the T + 1 passes from conv4_1 on as one batch (FcnEngine.mc_lowres_scores),
 and one kernel takes both experts' low-resolution scores to the fused labels (ops.variance_head)."""
-import torch
-
 from . import ops
-from .basic_fusion_model import FusionModel, run_trunks
+from .basic_fusion_model import FusionModel, mc_dropout_setup, output_key, per_expert_output, run_mc_lowres_scores
 
 
 def variance_fusion(probs, variances):
@@ -34,11 +32,7 @@ class VarianceFusion(FusionModel):
         standard_config.update(config)
         if 'prefixes' not in standard_config and 'modalities' in standard_config:
             standard_config['prefixes'] = {m: m for m in standard_config['modalities']}
-        for key in ('dropout_rate', 'num_samples'):
-            if key not in standard_config:
-                raise UserWarning('ERROR: VarianceFusion needs %s in its config' % key)
-        if standard_config.get('expert_model', 'fcn') != 'fcn':
-            raise UserWarning('ERROR: VarianceFusion samples FCN experts only (expert_model=%r)' % standard_config['expert_model'])
+        mc_dropout_setup('VarianceFusion', standard_config)
         standard_config['expert_model'] = 'fcn'
         FusionModel.__init__(self, 'VarianceFusion', output_dir=output_dir, **standard_config)
 
@@ -46,37 +40,20 @@ class VarianceFusion(FusionModel):
         FusionModel._build_graph(self)
         if len(self.modalities) != 2:
             raise UserWarning('ERROR: VarianceFusion fuses two experts, got %d' % len(self.modalities))
-        rate, T = float(self.config['dropout_rate']), int(self.config['num_samples'])
-        if not 0.0 <= rate < 1.0 or T < 1:
-            raise ValueError('dropout_rate must lie in [0, 1) and num_samples be at least 1')
-        for e in self.experts.values():
-            if not e.commuted_head():
-                raise NotImplementedError('VarianceFusion needs experts with the commuted decoder head (bilinear x8 deconv)')
-            e.mc_chunk_images = int(self.config.get('mc_chunk_images', 64))
-        seed = self.config.get('dropout_seed', self.config.get('seed'))
-        self._dropout_seed = int(seed) if seed is not None else 0
+        self._dropout_seed = mc_dropout_setup('VarianceFusion', self.config, engines=self.experts.values())[2]
 
     def _graph_capturable(self):
         return False
 
     def _predict_batch_impl(self, batch, output_attr=None):
-        inputs = {m: self._to_device(batch[m], torch.float32) for m in self.modalities}
-        rate, T = float(self.config['dropout_rate']), int(self.config['num_samples'])
-        seeds = {m: self._dropout_seed + i for i, m in enumerate(self.modalities)}     # independent masks per expert
-        # pair=False: the plain trunks stop at pool3 -- a paired section from conv4_1 on would skip the replication
-        res = run_trunks(self, inputs, lambda m, st: self.experts[m].mc_lowres_scores(inputs[m], T, rate, seeds[m], st=st),
-                         pair=False)
-        a, b = self.modalities
-        n, hi, wi = res[a][1]
-        out = ops.variance_head(res[a][0], res[b][0], self.experts[a].b['score'], self.experts[b].b['score'], n, hi, wi,
-                                self.config['num_classes'], T, want_score=output_attr in ('fused_score', 'score'),
-                                want_probs=output_attr in ('probs', 'prob'), want_variance=output_attr == 'variance')
+        key = output_key(output_attr)
+        out = ops.variance_head(*run_mc_lowres_scores(self, batch, 'mc_lowres_scores'), self.config['num_classes'],
+                                int(self.config['num_samples']), want_score=key == 'fused_score', want_probs=key == 'probs',
+                                want_variance=key == 'variance')
         if 'probs' in out:
-            self.probs = {m: out['probs'][i] for i, m in enumerate(self.modalities)}
-            return out['probs'].transpose(0, 1).contiguous()
+            return per_expert_output(self, out['probs'], keep='probs')
         if 'variance' in out:
-            self.variances = {m: out['variance'][i] for i, m in enumerate(self.modalities)}
-            return out['variance'].transpose(0, 1).contiguous()
+            return per_expert_output(self, out['variance'], keep='variances')
         if 'fused_score' in out:
             return out['fused_score']
         return out['label']
