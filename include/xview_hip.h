@@ -511,6 +511,16 @@ int xv_fused_head_joint_hist_fwd(const float* Sa, const float* Sb, const float* 
                                  int wi, int num_classes, const int32_t* labels, int64_t* hist, int max_workgroups,
                                  void* stream);
 
+/* The joint histogram per GROUP of images: arguments as xv_fused_head_joint_hist_fwd, group int32 [n] in DEVICE memory, hist
+ * int64 [num_groups][C][C][C]: hist[group[i]][label][a][b] += 1 with the experts' labels a, b bit for bit those of the
+ * ungrouped call (group g's slice is that call on g's images alone; the sum over the groups is that call on all of them);
+ * accumulated, not cleared.  Each workgroup handles one image at a time and flushes once per image; an id outside
+ * [0, num_groups) counts nothing.  XV_EINVAL as xv_fused_head_joint_hist_fwd (2..20 classes, labels 16-byte aligned), and for
+ * a null or misaligned group / hist or num_groups < 1.                                                                       */
+int xv_fused_head_joint_hist_grouped_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
+                                         int hi, int wi, int num_classes, const int32_t* labels, const int32_t* group,
+                                         int num_groups, int64_t* hist, int max_workgroups, void* stream);
+
 /* Fused average head of a two-expert fusion model (average_mix.py:18-21): Sa, Sb, biases, n, hi, wi, num_classes as
  * xv_fused_head_fwd takes them -> per output pixel both experts' softmax (bits of xv_decoder_head_fwd's prob), their sum
  * halved, and its first-maximum argmax -> fused_label int64 [n][8hi][8wi] (16-byte aligned): the labels of two
@@ -634,6 +644,15 @@ int xv_dirichlet_suffstats(const float* prob, const int32_t* labels, int num_cla
  * labels are the dropped (C+1)-th row); cm int64 [C][C], accumulated, rows = ground truth.         */
 int xv_confusion_matrix(const int32_t* labels, const int64_t* pred, int num_classes, int64_t npix,
                         int64_t* cm, void* stream);
+/* The same per GROUP of images (experiments/evaluation.py:42-55 scores once per sequence; a bootstrap over images needs a
+ * matrix per image): labels int32 / pred int64 [n][ppi] (n images of ppi pixels each), group int32 [n] in DEVICE memory,
+ * cm int64 [num_groups][C][C]: cm[group[i]][label][pred] += 1 over the pixels xv_confusion_matrix counts, accumulated, not
+ * cleared; summed over the groups it is xv_confusion_matrix of the same maps.  A workgroup counts one image at a time in its
+ * LDS and flushes with one atomic per non-zero cell; an image whose id is outside [0, num_groups) counts nothing.  The same
+ * class counts as xv_confusion_matrix (XV_ESHAPE beyond 64).  XV_EINVAL for a null pointer, n, ppi or num_groups below 1, or
+ * a pointer that is not aligned to its element.                                                                              */
+int xv_confusion_matrix_grouped(const int32_t* labels, const int64_t* pred, const int32_t* group, int n, int64_t ppi,
+                                int num_classes, int num_groups, int64_t* cm, void* stream);
 /* Uncertainty benchmarks on materialised maps (uncertainty_model.py): metric float [npix] (one uncertainty map), pred int64
  * [npix], labels int32 [npix].  hist uint64 [2][bins], bins = octaves << mantissa_bits: hist[row][bin(metric)] += 1 with
  * row = (pred != label) over the pixels with 0 <= label < C (fixed_row = -1), or row fixed_row (0 or 1) for EVERY pixel (pred

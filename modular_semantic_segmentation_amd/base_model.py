@@ -64,6 +64,85 @@ def score_measures(confusion_matrix):
     return measures
 
 
+def dense_group_ids(groups):
+    """(keys in the order they first appear, int64 id per image): the hashable keys of `groups` mapped to 0 .. G-1."""
+    keys, index, ids = [], {}, []
+    for key in groups:
+        if key not in index:
+            index[key] = len(keys)
+            keys.append(key)
+        ids.append(index[key])
+    return keys, np.asarray(ids, np.int64)
+
+
+def grouped_batches(model, data, ids, num_groups, max_iterations, scored):
+    """The labelled device batches of score() with each batch's slice of `ids` (one group id per image, in data order):
+    yields (batch, int32 labels on the device, int32 ids of the batch on the device).  The ids are checked and uploaded ONCE
+    (ops.upload_group_ids) and sliced there.  scored[0] counts the images that went by."""
+    from . import ops
+    dev_ids = ops.upload_group_ids(ids, num_groups, model.device)
+    for batch in model._device_batches(iterate_batches(data, model.config['batchsize'], max_iterations), labels=True):
+        n = len(batch['labels'])
+        if scored[0] + n > len(ids):
+            raise ValueError('groups names %d images, the data holds more' % len(ids))
+        yield batch, model._to_device(batch['labels'], torch.int32), dev_ids[scored[0]:scored[0] + n]
+        scored[0] += n
+
+
+def image_groups(data, groups, max_iterations, batchsize, across_ranks=False):
+    """(data, keys, ids) of a grouped pass: `groups` is one hashable key per image in data order, or the string 'image' (the
+    key is the running index of the image; data without a length is read into a list to count it).  across_ranks: every rank
+    scores its own shard and the counts are summed over the ranks, so the key table is agreed first (a collective): the union
+    of the ranks' keys in rank order, for 'image' the index over the shards in rank order (parallel.shard_data's order) -- slot
+    g then stands for the same group on every rank."""
+    from . import parallel
+    num_images = len(next(iter(data.values()))) if isinstance(data, dict) else (len(data) if hasattr(data, '__len__') else None)
+    if isinstance(groups, str):
+        if groups != 'image':
+            raise ValueError("groups is one key per image, or the string 'image'; got %r" % (groups,))
+        if num_images is None:
+            data = list(data)
+            num_images = len(data)
+        if max_iterations is not None:
+            num_images = min(num_images, max_iterations * batchsize)
+        first, total = parallel.agree_image_range(num_images) if across_ranks else (0, num_images)
+        return data, list(range(total)), np.arange(first, first + num_images, dtype=np.int64)
+    keys, ids = dense_group_ids(groups)
+    if across_ranks:
+        table = parallel.agree_group_keys(keys)
+        index = {key: g for g, key in enumerate(table)}
+        ids = np.asarray([index[key] for key in keys], np.int64)[ids]
+        keys = table
+    if num_images is not None and max_iterations is None and len(ids) != num_images:
+        raise ValueError('groups names %d images, the data holds %d' % (len(ids), num_images))
+    return data, keys, ids
+
+
+def groups_seen(model, ids, num_scored, num_groups):
+    """int64 [G]: how many scored images every group holds, summed over the ranks as the counts are."""
+    seen = np.bincount(ids[:num_scored], minlength=num_groups).astype(np.int64)
+    if model.config.get('reduce_score_over_ranks', False):
+        t = torch.from_numpy(seen).to(model.device)
+        reduce_over_ranks(model, t)
+        seen = t.cpu().numpy()
+    return seen
+
+
+def grouped_results(keys, ids, num_scored, confusion_matrices, complete=True, result=None, seen=None):
+    """{key: result(matrix of the key)} for the keys with a scored image, in the order of `keys`; result: by default (measures,
+    confusion matrix float64 [C, C]) as score() returns them.  complete: the pass was to see every image.  seen: images per
+    group (groups_seen: over all ranks, so that every rank returns every key); by default those of `ids`."""
+    if complete and num_scored != len(ids):
+        raise ValueError('groups names %d images, the data holds %d' % (len(ids), num_scored))
+    if result is None:
+        def result(cm):
+            cm = np.asarray(cm).astype(np.float64)
+            return score_measures(cm), cm
+    if seen is None:
+        seen = np.bincount(ids[:num_scored], minlength=len(keys))
+    return {keys[g]: result(confusion_matrices[g]) for g in np.flatnonzero(seen).tolist()}
+
+
 def reduce_over_ranks(model, *tensors):
     """Sum device tensors over the ranks, in place, where every rank counted its own shard of the data (config
     reduce_score_over_ranks: one process per GPU; a few KB each, RCCL all-reduce)."""
@@ -323,6 +402,34 @@ class BaseModel(object):
         reduce_over_ranks(self, cm_dev)
         confusion_matrix = cm_dev.cpu().numpy().astype(np.float64)
         return score_measures(confusion_matrix), confusion_matrix
+
+    def _count_groups(self, data, ids, num_groups, max_iterations, scored):
+        """int64 [G, C, C] on the host: every group's confusion matrix from ONE pass over `data` -- the labels score() counts
+        (the same captured step), counted per image into the group of its id.  The device matrix is kept across the batches,
+        summed over the ranks as score() sums its own (image_groups agreed the key table) and read back once."""
+        from . import ops
+        C = self.config['num_classes']
+        cm_dev = torch.zeros((num_groups, C, C), dtype=torch.int64, device=self.device)
+        state = {}
+        for batch, labels, batch_ids in grouped_batches(self, data, ids, num_groups, max_iterations, scored):
+            pred = self._predict_batch_auto(batch, None, state)
+            ops.confusion_matrix_grouped(labels, pred.contiguous(), batch_ids, num_groups, cm=cm_dev)
+        reduce_over_ranks(self, cm_dev)
+        return cm_dev.cpu().numpy()
+
+    def score_groups(self, data, groups, max_iterations=None):
+        """{key: (measures, confusion matrix)} from one pass over `data`, each pair what score() returns for the images of that
+        key alone (experiments/evaluation.py:42-55 scores once per sequence).  groups: one hashable key per image in data order,
+        or 'image' (the key is the running image index: a matrix per image, what a bootstrap resamples).  With max_iterations
+        only the keys of the scored images are returned."""
+        data, keys, ids = image_groups(data, groups, max_iterations, self.config['batchsize'],
+                                       across_ranks=self.config.get('reduce_score_over_ranks', False))
+        if not keys:
+            return {}
+        scored = [0]
+        counts = self._count_groups(data, ids, len(keys), max_iterations, scored)
+        return grouped_results(keys, ids, scored[0], counts, complete=max_iterations is None,
+                               seen=groups_seen(self, ids, scored[0], len(keys)))
 
     # ---- weights ----------------------------------------------------------------------------------------
     def _variables_changed(self):

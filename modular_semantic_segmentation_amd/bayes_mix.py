@@ -5,8 +5,9 @@ import numpy as np
 import torch
 
 from . import ops
+from .base_model import grouped_batches
 from .basic_fusion_model import (FusionModel, device_tables, fused_head_applicable, grid_point_configs, grid_results,
-                                 reduce_over_ranks, score_grid_fused, score_grid_generic)
+                                 reduce_over_ranks, run_lowres_scores, score_grid_fused, score_grid_generic)
 
 UNIFORM_PRIOR = 1.0 / 14     # the reference hard-codes 1/14 regardless of num_classes (bayes_mix.py:42,95)
 
@@ -174,3 +175,19 @@ class BayesFusion(FusionModel):
         counts = score_grid_generic(self, data, len(configs), ('classification',), fuse_point, max_iterations)
         reduce_over_ranks(self, counts)
         return grid_results(configs, counts.cpu().numpy())
+
+    # ---- a confusion matrix per group of images on one pass (BaseModel.score_groups) ----------------------
+    def _count_groups(self, data, ids, num_groups, max_iterations, scored):
+        """Where the fused head serves the model the trunks stop at their low-resolution class scores and the pass counts the
+        joint histogram per group; every group's matrix follows from it on the host as score_grid derives a prior's."""
+        C = self.config['num_classes']
+        if self.config.get('decision_matrix', False) or not fused_head_applicable(self) or C > self.JOINT_HIST_MAX_CLASSES:
+            return FusionModel._count_groups(self, data, ids, num_groups, max_iterations, scored)
+        hist = torch.zeros((num_groups, C, C, C), dtype=torch.int64, device=self.device)
+        for batch, labels, batch_ids in grouped_batches(self, data, ids, num_groups, max_iterations, scored):
+            Sa, Sb, ba, bb, n, hi, wi = run_lowres_scores(self, batch)
+            ops.fused_head_joint_hist_grouped(Sa, Sb, ba, bb, n, hi, wi, C, labels, batch_ids, num_groups, hist=hist)
+        reduce_over_ranks(self, hist)
+        mats = [self.confusion_matrices[m] for m in self.modalities]
+        decision = fused_decision_table(*bayes_tables(mats, self.config['class_prior']))
+        return np.stack([confusion_from_joint_hist(h, decision) for h in hist.cpu().numpy()])

@@ -13,6 +13,7 @@ from copy import deepcopy
 import numpy as np
 
 from . import get_model
+from .base_model import score_measures
 from .basic_fusion_model import parameter_combinations  # noqa: F401  (the reference's name, defined beside score_grid)
 from .bayes_mix import BayesFusion
 from .dirichlet_mix import DirichletFusion
@@ -54,6 +55,90 @@ def evaluate(net, testset, print_results=True, labelinfo=None):
                 labelinfo[label]['name'], measures['precision'][label], measures['recall'][label],
                 measures['IoU'][label]))
     return measures, confusion_matrix
+
+
+def evaluate_groups(net, testset, groups, print_results=True, labelinfo=None):
+    """evaluate() per group of images on ONE pass of the network (net.score_groups): {key: (measures, confusion matrix)}.
+    groups: one hashable key per image in the order of `testset`, or 'image'."""
+    results = net.score_groups(testset, groups)
+    if print_results:
+        for key, (measures, _) in results.items():
+            print('{}: total accuracy {:.3f} mean F1 {:.3f} IoU {:.3f}'.format(
+                key, measures['total_accuracy'], measures['mean_F1'], measures['mean_IoU']))
+            for label in (labelinfo or {}):
+                print('{:>15}: {:.2f} precision, {:.2f} recall, {:.2f} IoU'.format(
+                    labelinfo[label]['name'], measures['precision'][label], measures['recall'][label],
+                    measures['IoU'][label]))
+    return results
+
+
+def evaluate_on_all_sequences(net, testset, sequence_of_image):
+    """experiments/evaluation.py:42-55 (evaluate_on_all_synthia_seqs) on one pass instead of one evaluation per sequence:
+    sequence_of_image names the sequence of every image of `testset`, in order.  Returns {sequence: measures}."""
+    all_measurements = {}
+    for sequence, (measurements, _) in evaluate_groups(net, testset, sequence_of_image, print_results=False).items():
+        print('Evaluated network on {}: {:.2f} IoU'.format(sequence, measurements['mean_IoU']))
+        all_measurements[sequence] = measurements
+    return all_measurements
+
+
+def _resampled_measures(per_image_cms, counts, measure):
+    """The measure of every resample: counts int64 [R, N] (how often each image was drawn) times the images' matrices [N, C*C]
+    in int64, each sum through score_measures."""
+    cms = np.asarray(per_image_cms)
+    flat = cms.reshape(len(cms), -1).astype(np.int64)
+    sums = (counts @ flat).reshape((len(counts),) + cms.shape[1:])
+    return np.array([score_measures(cm)[measure] for cm in sums], np.float64)
+
+
+def _bootstrap_counts(num_images, num_resamples, seed):
+    """int64 [R, N]: per resample, how often each of N images is drawn in N draws with replacement -- one multinomial draw of
+    numpy.random.RandomState(seed) per resample, so `seed` fixes them."""
+    rng = np.random.RandomState(seed)
+    return rng.multinomial(num_images, np.full(num_images, 1.0 / num_images), size=num_resamples).astype(np.int64)
+
+
+def _percentile_bounds(samples, interval):
+    tail = 100.0 * (1.0 - interval) / 2.0
+    low, high = np.nanpercentile(samples, [tail, 100.0 - tail])
+    return float(low), float(high)
+
+
+def _as_matrices(per_image_cms):
+    """A score_groups result ({key: (measures, matrix)}) or a sequence of [C, C] matrices -> array [N, C, C]."""
+    if isinstance(per_image_cms, dict):
+        per_image_cms = [cm for _, cm in per_image_cms.values()]
+    cms = np.asarray(per_image_cms)
+    if cms.ndim != 3 or cms.shape[1] != cms.shape[2] or len(cms) < 1:
+        raise ValueError('per-image confusion matrices of shape %s, expected [N, C, C]' % (cms.shape,))
+    return cms
+
+
+def bootstrap_measure(per_image_cms, measure='mean_IoU', num_resamples=1000, seed=0, interval=0.95):
+    """Bootstrap interval of a scalar measure of score() over the images: per resample N images are drawn with replacement,
+    their confusion matrices summed and the measure taken from the sum (score_measures).  per_image_cms: [N, C, C] (or what
+    score_groups(..., 'image') returns).  Returns {'value': the measure of all images, 'low', 'high': the percentile bounds of
+    `interval`, 'samples': float64 [num_resamples]}.  `seed` fixes the draws: the same seed gives the same samples."""
+    cms = _as_matrices(per_image_cms)
+    samples = _resampled_measures(cms, _bootstrap_counts(len(cms), num_resamples, seed), measure)
+    low, high = _percentile_bounds(samples, interval)
+    return {'value': float(score_measures(cms.sum(0))[measure]), 'low': low, 'high': high, 'samples': samples}
+
+
+def paired_bootstrap(per_image_cms_a, per_image_cms_b, measure='mean_IoU', num_resamples=1000, seed=0, interval=0.95):
+    """bootstrap_measure of the difference a - b of two methods scored on the SAME images (two rows of
+    FusionComparison.score_all_groups(..., 'image')): every resample draws the same images for both.  Returns {'value', 'low',
+    'high', 'samples'} of the difference and 'fraction_a_better': the share of resamples with a > b.  `seed` fixes the draws."""
+    a, b = _as_matrices(per_image_cms_a), _as_matrices(per_image_cms_b)
+    if a.shape != b.shape:
+        raise ValueError('paired matrices of shapes %s and %s' % (a.shape, b.shape))
+    counts = _bootstrap_counts(len(a), num_resamples, seed)
+    samples_a, samples_b = _resampled_measures(a, counts, measure), _resampled_measures(b, counts, measure)
+    samples = samples_a - samples_b
+    low, high = _percentile_bounds(samples, interval)
+    value = float(score_measures(a.sum(0))[measure] - score_measures(b.sum(0))[measure])
+    return {'value': value, 'low': low, 'high': high, 'samples': samples,
+            'fraction_a_better': float(np.mean(samples_a > samples_b))}
 
 
 def train_and_evaluate(modelname, net_config, data_description, trainset, testset, num_iterations, starting_weights=None,

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .base_model import score_measures
+from .base_model import grouped_batches, grouped_results, groups_seen, image_groups, score_measures
 from .basic_fusion_model import (FusionModel, _labelled_batches, device_tables, fused_head_applicable, measure_experts,
                                  reduce_over_ranks, run_experts, run_lowres_scores)
 from .bayes_mix import BayesFusion, bayes_tables, confusion_from_joint_hist, fused_decision_table
@@ -93,14 +93,37 @@ class FusionComparison(FusionModel):
     def one_pass_heads_applicable(self):
         return fused_head_applicable(self) and self.config['num_classes'] <= BayesFusion.JOINT_HIST_MAX_CLASSES
 
+    def _require_measurements(self):
+        if self.bayes is None or self.dirichlet is None:
+            raise UserWarning('ERROR: FusionComparison has no measurements yet, call fit() first')
+
+    def _row_names(self):
+        return list(self.modalities) + list(FUSIONS)
+
+    def _rows(self, matrices):
+        """{row name: (measures, confusion matrix float64)} from one matrix per row, each pair as score() returns it."""
+        out = {}
+        for name, cm in zip(self._row_names(), matrices):
+            cm = np.asarray(cm).astype(np.float64)
+            out[name] = (score_measures(cm), cm)
+        return out
+
+    def _generic_label_maps(self, batch):
+        """The generic route of one batch: every expert once with labels and probabilities, then the stand-alone fusion
+        kernels -> the five label maps, in row order."""
+        am1, lognorm, logprior = self.dirichlet
+        outs = run_experts(self, batch, ('classification', 'prob'))
+        labs = [outs[m]['classification'].contiguous() for m in self.modalities]
+        probs = [outs[m]['prob'] for m in self.modalities]
+        fused = [ops.bayes_fuse(labs, self.bayes[2], self.bayes[3])[0], ops.dirichlet_fuse(probs, am1, lognorm, logprior)[0],
+                 ops.average_fuse(probs)]
+        return labs + [pred.contiguous() for pred in fused]
+
     def score_all(self, test_set, max_iterations=None):
         """One pass of the experts over `test_set`: {modality: (measures, confusion matrix), ..., 'bayes_fusion': ...,
         'dirichlet_fusion': ..., 'average_fusion': ...}, each pair what score() of the single model returns."""
-        if self.bayes is None or self.dirichlet is None:
-            raise UserWarning('ERROR: FusionComparison has no measurements yet, call fit() first')
+        self._require_measurements()
         C = self.config['num_classes']
-        mods = self.modalities
-        names = list(mods) + list(FUSIONS)
         am1, lognorm, logprior = self.dirichlet
         if self.one_pass_heads_applicable():
             hist = torch.zeros((C, C, C), dtype=torch.int64, device=self.device)
@@ -117,19 +140,48 @@ class FusionComparison(FusionModel):
             bayes = confusion_from_joint_hist(hist, fused_decision_table(self.bayes[0], self.bayes[1]))
             matrices = [cm_a, cm_b, bayes, counts[0], counts[1]]
         else:
-            counts = torch.zeros((len(names), C, C), dtype=torch.int64, device=self.device)
+            counts = torch.zeros((len(self._row_names()), C, C), dtype=torch.int64, device=self.device)
             for batch, labels in _labelled_batches(self, test_set, max_iterations):
-                outs = run_experts(self, batch, ('classification', 'prob'))
-                labs = [outs[m]['classification'].contiguous() for m in mods]
-                probs = [outs[m]['prob'] for m in mods]
-                fused = labs + [ops.bayes_fuse(labs, self.bayes[2], self.bayes[3])[0],
-                                ops.dirichlet_fuse(probs, am1, lognorm, logprior)[0], ops.average_fuse(probs)]
-                for i, pred in enumerate(fused):
-                    ops.confusion_matrix(labels, pred.contiguous(), counts[i])
+                for i, pred in enumerate(self._generic_label_maps(batch)):
+                    ops.confusion_matrix(labels, pred, counts[i])
             reduce_over_ranks(self, counts)
             matrices = list(counts.cpu().numpy())
-        out = {}
-        for name, cm in zip(names, matrices):
-            cm = np.asarray(cm).astype(np.float64)
-            out[name] = (score_measures(cm), cm)
-        return out
+        return self._rows(matrices)
+
+    def score_all_groups(self, test_set, groups, max_iterations=None):
+        """score_all per group of images on ONE pass of the experts: {key: what score_all returns for the images of that key}.
+        groups as BaseModel.score_groups takes them: one hashable key per image in data order, or 'image'.  On the one-pass
+        heads the grouped joint histogram gives both experts and Bayes; the Dirichlet and the average label maps (fused heads)
+        are counted by the grouped confusion kernel."""
+        self._require_measurements()
+        C = self.config['num_classes']
+        am1, lognorm, logprior = self.dirichlet
+        test_set, keys, ids = image_groups(test_set, groups, max_iterations, self.config['batchsize'],
+                                           across_ranks=self.config.get('reduce_score_over_ranks', False))
+        G, scored = len(keys), [0]
+        if not keys:
+            return {}
+        if self.one_pass_heads_applicable():
+            hist = torch.zeros((G, C, C, C), dtype=torch.int64, device=self.device)
+            counts = torch.zeros((2, G, C, C), dtype=torch.int64, device=self.device)      # Dirichlet, average
+            for batch, labels, batch_ids in grouped_batches(self, test_set, ids, G, max_iterations, scored):
+                Sa, Sb, ba, bb, n, hi, wi = run_lowres_scores(self, batch)
+                ops.fused_head_joint_hist_grouped(Sa, Sb, ba, bb, n, hi, wi, C, labels, batch_ids, G, hist=hist)
+                fused = ops.fused_head(Sa, Sb, ba, bb, n, hi, wi, C, am1, logprior, lognorm=lognorm)
+                ops.confusion_matrix_grouped(labels, fused, batch_ids, G, cm=counts[0])
+                fused = ops.fused_head_average(Sa, Sb, ba, bb, n, hi, wi, C)
+                ops.confusion_matrix_grouped(labels, fused, batch_ids, G, cm=counts[1])
+            reduce_over_ranks(self, hist, counts)
+            hist, counts = hist.cpu().numpy(), counts.cpu().numpy()
+            decision = fused_decision_table(self.bayes[0], self.bayes[1])
+            matrices = [list(expert_matrices_from_joint_hist(hist[g])) + [confusion_from_joint_hist(hist[g], decision),
+                                                                         counts[0][g], counts[1][g]] for g in range(G)]
+        else:
+            counts = torch.zeros((len(self._row_names()), G, C, C), dtype=torch.int64, device=self.device)
+            for batch, labels, batch_ids in grouped_batches(self, test_set, ids, G, max_iterations, scored):
+                for i, pred in enumerate(self._generic_label_maps(batch)):
+                    ops.confusion_matrix_grouped(labels, pred, batch_ids, G, cm=counts[i])
+            reduce_over_ranks(self, counts)
+            matrices = counts.cpu().numpy().transpose(1, 0, 2, 3)
+        return grouped_results(keys, ids, scored[0], matrices, complete=max_iterations is None, result=self._rows,
+                               seen=groups_seen(self, ids, scored[0], G))

@@ -5,6 +5,7 @@ hot path runs in libxview_hip.so.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -670,6 +671,57 @@ def fused_head_joint_hist(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels
     return hist
 
 
+def upload_group_ids(groups, num_groups, device):
+    """One group id per image (a host sequence, numpy array or CPU tensor), checked HERE -- integers, every one in
+    [0, num_groups) -- and uploaded as the int32 tensor the grouped kernels index with.  A pass over many batches calls this
+    once for all its images and hands the grouped ops slices of the result."""
+    G = int(num_groups)
+    if G < 1:
+        raise ValueError('num_groups must be at least 1, got %d' % G)
+    ids = np.asarray(groups.cpu() if isinstance(groups, torch.Tensor) else groups)
+    if ids.ndim != 1 or ids.dtype.kind not in 'iu':
+        raise ValueError('groups must be integers, one per image, got shape %s of dtype %s' % (ids.shape, ids.dtype))
+    if ids.size and (ids.min() < 0 or ids.max() >= G):
+        raise ValueError('group ids must lie in [0, %d), got %d .. %d' % (G, ids.min(), ids.max()))
+    return torch.from_numpy(ids.astype(np.int32)).to(device)
+
+
+def _group_ids(groups, n, num_groups, device):
+    """The int32 [n] device tensor of a grouped launch: `groups` from the host goes through upload_group_ids; a CUDA int32
+    tensor is taken as (a slice of) what upload_group_ids returned -- checked there, only its length is checked here."""
+    if isinstance(groups, torch.Tensor) and groups.is_cuda:
+        _need(groups, torch.int32, 'groups')
+        if int(num_groups) < 1 or tuple(groups.shape) != (n,):
+            raise ValueError('groups of shape %s for %d images and %d groups' % (tuple(groups.shape), n, int(num_groups)))
+        return groups
+    ids = upload_group_ids(groups, num_groups, device)
+    if ids.numel() != n:
+        raise ValueError('groups must be %d integers (one per image), got %d' % (n, ids.numel()))
+    return ids
+
+
+def fused_head_joint_hist_grouped(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, groups, num_groups, hist=None,
+                                  max_workgroups=0):
+    """fused_head_joint_hist per group of images: `groups` holds one id in [0, num_groups) per image (host side: checked here
+    before anything is launched; or a device slice of upload_group_ids' result); accumulates into hist (int64 [G,C,C,C]; made here, zeroed, when None) and returns it."""
+    C, G = int(num_classes), int(num_groups)
+    _check_lowres_pair(Sa, Sb, n, hi, wi, C, labels)
+    _need(bias_a, torch.float32, 'bias_a')
+    _need(bias_b, torch.float32, 'bias_b')
+    ids = _group_ids(groups, n, G, Sa.device)
+    if labels.data_ptr() & 15:            # (a slice of a larger map: the kernel reads label quads with 16-byte loads)
+        labels = labels.clone()
+    if hist is None:
+        hist = torch.zeros((G, C, C, C), dtype=torch.int64, device=Sa.device)
+    _need(hist, torch.int64, 'hist')
+    if tuple(hist.shape) != (G, C, C, C):
+        raise ValueError('hist of shape %s, expected %s' % (tuple(hist.shape), (G, C, C, C)))
+    rc = _lib.lib().xv_fused_head_joint_hist_grouped_fwd(_ptr(Sa), _ptr(Sb), _ptr(bias_a), _ptr(bias_b), n, hi, wi, C,
+                                                        _ptr(labels), _ptr(ids), G, _ptr(hist), int(max_workgroups), _stream())
+    _lib.check(rc, 'xv_fused_head_joint_hist_grouped_fwd')
+    return hist
+
+
 def fused_head_average(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, out=None):
     """Both experts' low-resolution scores -> the average-fused label map (int64 [n, 8hi, 8wi]): the labels of average_fuse on
     the two probability maps decoder_head_from_scores writes, without those maps."""
@@ -1076,6 +1128,31 @@ def confusion_matrix(labels, pred, cm):
     _need(cm, torch.int64, 'cm')
     rc = _lib.lib().xv_confusion_matrix(_ptr(labels), _ptr(pred), cm.shape[0], labels.numel(), _ptr(cm), _stream())
     _lib.check(rc, 'xv_confusion_matrix')
+
+
+def confusion_matrix_grouped(labels, pred, groups, num_groups, cm=None, num_classes=None):
+    """confusion_matrix per group of images: labels int32 / pred int64 [n, ...] with the image axis first, `groups` one id in
+    [0, num_groups) per image (host side: checked here before anything is launched; or a device slice of upload_group_ids'
+    result).  Accumulates into cm (int64 [G,C,C], rows = ground truth) and returns it; with cm=None a zeroed one is made here,
+    for which the class count has to be named: `num_classes` (the maps do not carry it)."""
+    _need(labels, torch.int32, 'labels')
+    _need(pred, torch.int64, 'pred')
+    G = int(num_groups)
+    if labels.dim() < 2 or labels.shape != pred.shape or labels.numel() == 0:
+        raise ValueError('labels %s and pred %s must be equal non-empty shapes [n, ...]' % (tuple(labels.shape), tuple(pred.shape)))
+    n = labels.shape[0]
+    ids = _group_ids(groups, n, G, labels.device)
+    if cm is None:
+        if num_classes is None:
+            raise ValueError('confusion_matrix_grouped makes cm itself only when told num_classes')
+        cm = torch.zeros((G, int(num_classes), int(num_classes)), dtype=torch.int64, device=labels.device)
+    _need(cm, torch.int64, 'cm')
+    if cm.dim() != 3 or cm.shape[0] != G or cm.shape[1] != cm.shape[2] or (num_classes is not None and cm.shape[1] != num_classes):
+        raise ValueError('cm of shape %s, expected [%d, C, C]' % (tuple(cm.shape), G))
+    rc = _lib.lib().xv_confusion_matrix_grouped(_ptr(labels), _ptr(pred), _ptr(ids), n, labels.numel() // n, cm.shape[1], G,
+                                               _ptr(cm), _stream())
+    _lib.check(rc, 'xv_confusion_matrix_grouped')
+    return cm
 
 
 # ---- training ----------------------------------------------------------------------------------------

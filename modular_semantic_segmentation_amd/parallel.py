@@ -38,6 +38,36 @@ def allreduce_sum_(*tensors):
     return tensors
 
 
+def agree_group_keys(keys):
+    """One key table for every rank of a grouped scoring pass (BaseModel.score_groups under reduce_score_over_ranks): `keys` =
+    this rank's keys in the order they first appear in its shard; returns the union over the ranks, rank 0's keys first, then
+    what rank 1 adds, ... -- the same list on every rank, so that slot g of the reduced [G, ...] tensors stands for ONE group
+    everywhere.  A single process gets its own keys back."""
+    _, size = world()
+    if size == 1:
+        return list(keys)
+    gathered = [None] * size
+    dist.all_gather_object(gathered, list(keys))
+    table, known = [], set()
+    for rank_keys in gathered:
+        for key in rank_keys:
+            if key not in known:
+                known.add(key)
+                table.append(key)
+    return table
+
+
+def agree_image_range(num_images):
+    """(first global index of this rank's images, number of images of all ranks) for contiguous shards in rank order
+    (shard_data): the running image index of a grouped pass, agreed over the ranks.  (0, num_images) for a single process."""
+    rank, size = world()
+    if size == 1:
+        return 0, int(num_images)
+    gathered = [None] * size
+    dist.all_gather_object(gathered, int(num_images))
+    return sum(gathered[:rank]), sum(gathered)
+
+
 _STATS_GROUP = {}
 
 
