@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .base_model import BaseModel
 from .custom_layers import bilinear_filter, dense_deconv_as_conv3x3
-from .fcn import BN_EPS
+from .fcn import BN_EPS, Arena, check_variables
 
 # (scope, kind, arguments): a = (intermediate, filters, stride, shortcut_conv),
 # b = (filters_1, filters_2, filters_3, dilation1, dilation2, shortcut_conv)           adapnet.py:130-155
@@ -139,7 +139,7 @@ def dilated_pair_as_1x1(kernel1, kernel2):
     return out
 
 
-class AdapnetEngine(object):
+class AdapnetEngine(Arena):
     """One AdapNet expert resident on one GPU; same surface as fcn.FcnEngine (load / forward)."""
 
     def __init__(self, prefix, in_channels, num_units, num_classes, variables, device='cuda', blocks=None):
@@ -158,11 +158,7 @@ class AdapnetEngine(object):
     def load(self, variables):
         p, dev = self.prefix, self.device
         v = {k: np.asarray(a, np.float32) for k, a in variables.items() if k.startswith(p + '/')}
-        for need, shape in variable_shapes(p, self.cin, self.U, self.C, self.blocks).items():
-            if need not in v:
-                raise KeyError('missing variable %s' % need)
-            if tuple(v[need].shape) != tuple(shape):
-                raise ValueError('variable %s has shape %s, expected %s' % (need, v[need].shape, shape))
+        check_variables(v, variable_shapes(p, self.cin, self.U, self.C, self.blocks))
         # which of the two deconv kernels is still the bilinear constant (fast depthwise forms) and which is dense
         self.dense = {}
         dense_scopes = [scope for scope in ('first_deconvolution_upconv', 'second_deconvolution_upconv')
@@ -239,15 +235,6 @@ class AdapnetEngine(object):
         ws[np.arange(self.C), np.arange(self.C)] = s
         self.w['score'], self.b['score'] = up(ws), up(t)
         torch.cuda.synchronize(dev)
-
-    # ---- activations -----------------------------------------------------------------------------------------
-    def _act(self, name, n, h, w, c):
-        key = (name, n, h, w, c)
-        a = self._arena.get(key)
-        if a is None:
-            a = ops.Act(n, h, w, c, self.device)
-            self._arena[key] = a
-        return a
 
     def _conv(self, name, x, k, cout, relu=True):
         y = self._act(name, x.n, x.h, x.w, cout)

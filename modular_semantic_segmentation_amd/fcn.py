@@ -129,6 +129,104 @@ def _fold_bn(variables, layer, kernel, bias):
     return kernel * s, (bias - variables[layer + '/moving_mean']) * s + variables[layer + '/beta']
 
 
+def check_variables(v, shapes):
+    """Every variable of `shapes` (name -> shape) is in the dict `v`, with that shape."""
+    for need, shape in shapes.items():
+        if need not in v:
+            raise KeyError('missing variable %s' % need)
+        if tuple(np.shape(v[need])) != tuple(shape):
+            raise ValueError('variable %s has shape %s, expected %s' % (need, np.shape(v[need]), shape))
+
+
+def upload(a, device):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+# ---- the decoder tail of FcnEngine and fusion_fcn.FusionFcnEngine: weights --------------------------------------------------
+def dense_deconv_weights(kern, stride, U, Up, device):
+    """The reference never trains its deconvs (simple_fcn.py:80-83,117-119; fusion_fcn.py:26-31), so their kernels are the
+    bilinear constant and run as depthwise interpolations: None.  An imported kernel that is anything else takes the dense
+    transposed-conv path (xv_deconv_dense_fwd on the MFMA conv; the decoder head is then the un-commuted one): its 3x3 phase
+    weights, padded to Up units and packed, and their zero bias."""
+    if is_bilinear_filter(kern):
+        return None
+    kp = np.zeros((kern.shape[0], kern.shape[1], Up, Up), np.float32)
+    kp[:, :, :U, :U] = kern                                 # padding units: zero rows and columns
+    k3 = torch.from_numpy(dense_deconv_as_conv3x3(kp, stride)).to(device)
+    return ops.pack_conv_weights(k3), torch.zeros(stride * stride * Up, dtype=torch.float32, device=device)
+
+
+def deconv_batch_norm(v, layer, U, Up, device, dense):
+    """Batch norm after a deconv (custom_layers.py:112-119) is a per-channel affine before its relu: (scale, affine).  A
+    positive scale with zero shift commutes with the relu and the (linear, bilinear: not `dense`) deconv: `scale`, for the
+    caller to fold into the 1x1 conv on the other side.  Anything else goes through the affine forms of the x2 kernel and of
+    the decoder head (the un-commuted one: 16x the FMAs of the default head): `affine`, padded to Up.  No batch norm: neither."""
+    if layer + '/gamma' not in v:
+        return None, None
+    s = v[layer + '/gamma'] / np.sqrt(v[layer + '/moving_variance'] + BN_EPS)
+    t = v[layer + '/beta'] - v[layer + '/moving_mean'] * s
+    if np.all(s > 0) and np.all(np.abs(t) <= 1e-12) and not dense:
+        return s.astype(np.float32), None
+    sp, tp = np.ones(Up, np.float32), np.zeros(Up, np.float32)
+    sp[:U], tp[:U] = s, t                                   # padding channels: relu(0 * 1 + 0) = 0
+    return None, (upload(sp, device), upload(tp, device))
+
+
+def padded_score_conv(k, b, U, Up):
+    """A 1x1 score conv [1,1,cin,U] (cin: 512 per trunk) padded to Up lanes of zeros: the score convs run on the MFMA kernel."""
+    kp = np.zeros((1, 1, k.shape[2], Up), np.float32)
+    kp[..., :U] = k
+    bp = np.zeros(Up, np.float32)
+    bp[:U] = b
+    return kp, bp
+
+
+def padded_score_matrix(k, Up, device):
+    """The class-score matrix [U,C] of the decoder head with zero rows for the padding units, on the device."""
+    ws = np.zeros((Up, k.shape[1]), np.float32)
+    ws[:k.shape[0]] = k
+    return upload(ws, device)
+
+
+# ---- the decoder tail: launches (e: the engine -- _act, _arena, Up, C, w['score'], b['score']) -------------------------------
+def upsample2x_skip(e, s5, s4, y, dense, affine):
+    """y = relu(x2 deconv of s5 [batch norm `affine`]) + s4; dense: dense_deconv_weights of the deconv kernel"""
+    scale, shift = affine or (None, None)
+    if dense is not None:
+        wk, zb = dense
+        _, e._arena['dd_ws5'] = ops.deconv_dense_fwd(s5, wk, zb, 2, e.Up, y=y, scale=scale, shift=shift, residual=s4, relu=True,
+                                                    workspace=e._arena.get('dd_ws5'))
+    else:
+        ops.upsample2x_relu_add(s5, residual=s4, y=y, scale=scale, shift=shift)
+    return y
+
+
+def decoder_head(e, f, want, dense, affine, layers, workspace=None):
+    """The head, from the decoder's input `f` to a dict with the wanted 'score' / 'prob' (float32 [N,H,W,C]) / 'label' (int64
+    [N,H,W]): ONE kernel, or with a `dense` x8 deconv kernel the dense deconv -> [batch norm] -> relu at full resolution
+    (layers['upscore']), then the per-pixel score conv, softmax, argmax."""
+    scale, shift = affine or (None, None)
+    want_label = 'label' in want or 'classification' in want
+    if dense is None:
+        return ops.decoder_head_fwd(f, e.w['score'], e.b['score'], e.C, want_score='score' in want, want_prob='prob' in want,
+                                    want_label=want_label, workspace=workspace, scale=scale, shift=shift)
+    wk, zb = dense
+    up = layers['upscore'] = e._act('upscore', f.n, 8 * f.h, 8 * f.w, e.Up)
+    _, e._arena['dd_ws'] = ops.deconv_dense_fwd(f, wk, zb, 8, e.Up, y=up, scale=scale, shift=shift, relu=True,
+                                               workspace=e._arena.get('dd_ws'))
+    skey = ('dense_score', f.n, f.h, f.w)
+    if skey not in e._arena:
+        e._arena[skey] = torch.empty((f.n, 8 * f.h, 8 * f.w, e.C), dtype=torch.float32, device=e.device)
+    score = ops.score_dense_fwd(up, e.w['score'], e.b['score'], e.C, e._arena[skey])
+    prob, label = ops.softmax_argmax(score, want_prob='prob' in want, want_label=want_label)
+    out = {'score': score} if 'score' in want else {}
+    if prob is not None:
+        out['prob'] = prob
+    if label is not None:
+        out['label'] = label
+    return out
+
+
 # The two experts of a fusion model run the same layer shapes from conv1_2 on.  From this layer on each 3x3 layer of both is
 # ONE launch (ops.conv2d_fwd_pair: whole rounds of workgroups where each expert alone leaves its last round half empty).
 # (A test seam: another layer name moves the start, a name that is no layer keeps every launch per expert -- same bits.)
@@ -156,8 +254,141 @@ def encoder_layers_pair(ea, sa, eb, sb):
         eb._layer_done(sb, idx, yb, qb)
 
 
-class FcnEngine(object):
+class Arena(object):
+    """An engine's device buffers, kept from call to call in the plain dict `self._arena` (on `self.device`): activations by
+    name, shape and dtype; route buffers and workspaces under keys of their own."""
+
+    def _act(self, name, n, h, w, c, dtype='bf16', scale_exp=0):
+        key = (name, n, h, w, c, dtype)
+        a = self._arena.get(key)
+        if a is None:
+            a = ops.Act(n, h, w, c, self.device, dtype=dtype, scale_exp=scale_exp)
+            self._arena[key] = a
+        elif a.scale_exp != scale_exp:
+            a.set_scale_exp(scale_exp)
+        return a
+
+
+class Vgg16Walk(Arena):
+    """The 13 convs of ENCODER (pool1..pool4 fused into the conv epilogues) over a host object with `cin`, the weights `w` /
+    `b` by layer name and an arena: the ONLY walk of the trunk -- the FCN expert in bf16 and fp8, alone or paired with a twin
+    (encoder_layers_pair), and the trunks of the joint model (fusion_fcn.VggTrunk).  In steps over a state dict, so that a
+    fusion model can pair launches and the MC-dropout samplers can resume a state: encoder_begin (input checks, the first
+    conv(s), the layers before `stop`), then encoder_layers.  What differs between the callers are these options:"""
+    streamk = False         # hand the 3x3 convs of a bf16 walk a stream-K workspace (_sk)
+    split_small = False     # un-pooled layers of a bf16 walk: the split form where the tiles fill less than half the CUs
+
+    def _drop_fn(self):
+        """The dropout sites of the walk: a function (Act, tag) -> dropped Act, or None"""
+        return None
+
+    def _fp8_plan(self, x):
+        """(convs with e4m3 operands, conv outputs stored as e4m3) of a walk over x: see fp8_plan(); ((), ()) is bf16"""
+        return (), ()
+
+    def _sk(self):
+        """This engine's stream-K workspace (ops.streamk_workspace: arrival counters + partial-tile slabs of the
+        generation-2 conv kernel's tail round).  One per engine: the two experts of a fusion model run on two streams."""
+        if not self.streamk:
+            return None
+        ws = self._arena.get('streamk_ws')
+        if ws is None:
+            ws = self._arena['streamk_ws'] = ops.streamk_workspace(self.device)
+        return ws
+
+    def _state(self, n, h, w, cur=None, next=0, keep_all=False, routed=False, plan=((), ())):
+        """The state of a walk over n images of h x w that has come to layer `next` with the map `cur`"""
+        return {'n': n, 'h': h, 'w': w, 'keep_all': keep_all, 'routed': routed, 'convs8': plan[0], 'maps8': plan[1], 'L': {},
+                'cur': cur, 'ch': cur.h if cur is not None else h, 'cw': cur.w if cur is not None else w, 'next': next}
+
+    def _weights(self, st, name):
+        return self.w8[name] if name in st['convs8'] else self.w[name]
+
+    def _stored(self, st, name):
+        """dtype / scale_exp of the maps conv `name` writes (a pool inherits its conv's scale), as _act arguments"""
+        return dict(dtype='fp8', scale_exp=self.fp8_scales[name]) if name in st['maps8'] else {}
+
+    def encoder_begin(self, x, keep_all=False, stop=None, routed=False):
+        n, h, w, cin = x.shape
+        if cin != self.cin:
+            raise ValueError('expected %d input channels, got %d' % (self.cin, cin))
+        if h % 16 or w % 16:
+            raise ValueError('H and W must be multiples of 16 (augmentation.py:244-262 crop_multiple)')
+        plan = convs8, maps8 = self._fp8_plan(x)
+        # route bytes: the training step's (keep_all) bf16 walk only
+        st = self._state(n, h, w, keep_all=keep_all, routed=bool(routed) and keep_all and not maps8, plan=plan)
+        x = x.contiguous()
+        # conv1_1 + conv1_2 + pool1 in one launch where neither full-resolution map is wanted (inference): conv1_1 is
+        # evaluated straight into conv1_2's LDS patch buffers (csrc/conv_first_fused.hip; the same bits as the two kernels,
+        # also in its e4m3-out form).  Maps that do not tile in 16x32 take the two kernels, and so does an fp8 plan that stores
+        # conv1_1 as e4m3 or gives conv1_2 e4m3 operands.  (fp8_start behind conv2_1: pool1 stays bf16.)
+        if not keep_all and 'conv1_1' not in maps8 and 'conv1_2' not in convs8 and \
+                ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
+            q = self._act('pool1', n, h // 2, w // 2, 64, **self._stored(st, 'conv1_2'))
+            if ops.conv_first_pair_fwd(x, self.w['conv1_1'], self.b['conv1_1'], self.w['conv1_2'], self.b['conv1_2'], pooled=q):
+                st['L']['pool1'] = st['cur'] = q
+                st.update(ch=h // 2, cw=w // 2, next=2)
+        if st['next'] == 0:
+            y = self._act('conv1_1', n, h, w, 64, **self._stored(st, 'conv1_1'))
+            ops.conv2d_first_fwd(x, self.w['conv1_1'], self.b['conv1_1'], y, relu=True)
+            st['L']['conv1_1'] = st['cur'] = y
+            st['next'] = 1
+        self.encoder_layers(st, len(ENCODER) if stop is None else stop)
+        return st
+
+    def _layer_outputs(self, st, idx):
+        """(full map or None, pooled map or None) of encoder layer idx"""
+        name, cout, pool = ENCODER[idx]
+        n, ch, cw, kw = st['n'], st['ch'], st['cw'], self._stored(st, name)
+        if pool is None:
+            return self._act(name, n, ch, cw, cout, **kw), None
+        need_full = st['keep_all'] or name == 'conv4_3'       # conv4_3 feeds score_conv4
+        return (self._act(name, n, ch, cw, cout, **kw) if need_full else None), self._act(pool, n, ch // 2, cw // 2, cout, **kw)
+
+    def _layer_done(self, st, idx, y, q):
+        name, cout, pool = ENCODER[idx]
+        L = st['L']
+        if pool is None:
+            L[name] = st['cur'] = y
+        else:
+            if y is not None:
+                L[name] = y
+            L[pool] = st['cur'] = q
+            st['ch'], st['cw'] = st['ch'] // 2, st['cw'] // 2
+            # simple_fcn.py:51-63: the dropout after pool4 is gated by 'pool3' too (a quirk of the reference:
+            # 'pool4' alone enables nothing)
+            drop = self._drop_fn()
+            if drop is not None and pool in ('pool3', 'pool4') and 'pool3' in self.dropout_layers:
+                L[pool + '_drop'] = st['cur'] = drop(q, pool + '_drop')
+        st['next'] = idx + 1
+
+    def encoder_layers(self, st, stop):
+        """encoder layers [st['next'], stop), one launch each"""
+        bf16 = not st['maps8']
+        for idx in range(st['next'], stop):
+            name = ENCODER[idx][0]
+            y, q = self._layer_outputs(st, idx)
+            # routed: a conv in front of a pool whose full map only MaxPoolGrad would read leaves the pool's route bytes instead
+            # (never conv4_3: it feeds score_conv4)
+            if st['routed'] and q is not None and name != 'conv4_3' and self._drop_fn() is None:
+                key = ('route_' + name, st['n'], q.h, q.w, q.c)
+                route = self._arena.get(key)
+                if route is None:
+                    route = self._arena[key] = torch.empty(st['n'] * q.h * q.w * q.c, dtype=torch.uint8, device=self.device)
+                if ops.conv2d_fwd_route(st['cur'], self.w[name], self.b[name], q, route):
+                    st['L']['route_' + name] = route
+                    self._layer_done(st, idx, None, q)
+                    continue
+            split = self.split_small and bf16 and q is None
+            ops.conv2d_fwd(st['cur'], self._weights(st, name), self.b[name], 3, relu=True, y=y, pooled=q, write_y=y is not None,
+                           workspace=self._sk() if bf16 else None,
+                           split_ws=ops.split_workspace(st['cur'], ENCODER[idx][1], self._arena) if split else None)
+            self._layer_done(st, idx, y, q)
+
+
+class FcnEngine(Vgg16Walk):
     """One FCN expert resident on one GPU (inference graph of simple_fcn.py:137-170)."""
+    split_small = True
 
     def __init__(self, prefix, in_channels, num_units, num_classes, variables, device='cuda', conv_dtype='bf16',
                  streamk=False, fp8_deep=False, fp8_start=None):
@@ -206,101 +437,42 @@ class FcnEngine(object):
             # a plan calibrate_guarded() chose was chosen FOR THE OLD WEIGHTS: back to the default plan until it is called again
             self.fp8_off, self.fp8_start, self.fp8_guard = False, None, None
         v = {k: np.asarray(a, np.float32) for k, a in variables.items() if k.startswith(p + '/')}
-        for need, shape in variable_shapes(p, self.cin, self.U, self.C).items():
-            if need not in v:
-                raise KeyError('missing variable %s' % need)
-            if tuple(v[need].shape) != tuple(shape):
-                raise ValueError('variable %s has shape %s, expected %s' % (need, v[need].shape, shape))
-        # The reference never trains its deconvs (simple_fcn.py:80-83,117-119), so their kernels are the bilinear
-        # constant and run as depthwise interpolations.  An imported kernel that is anything else takes the dense
-        # transposed-conv path (xv_deconv_dense_fwd on the MFMA conv; the decoder head is then the un-commuted one).
-        self.dense_deconv = {}
+        check_variables(v, variable_shapes(p, self.cin, self.U, self.C))
+        self.dense_deconv, deconv_scale, self.affine = {}, {}, {}
         for name, stride in (('upscore_conv5', 2), ('upscore', 8)):
-            kern = v['%s/%s/kernel' % (p, name)]
-            if not is_bilinear_filter(kern):
-                kp = np.zeros((kern.shape[0], kern.shape[1], self.Up, self.Up), np.float32)
-                kp[:, :, :self.U, :self.U] = kern                       # padding units: zero rows and columns
-                k3 = torch.from_numpy(dense_deconv_as_conv3x3(kp, stride)).to(dev)
-                self.dense_deconv[name] = (ops.pack_conv_weights(k3),
-                                           torch.zeros(stride * stride * self.Up, dtype=torch.float32, device=dev))
-        # Batch norm after a deconv (custom_layers.py:112-119) is a per-channel affine before its relu.  A
-        # positive scale with zero shift commutes with the relu and the (linear) deconv and is folded into
-        # the 1x1 conv on the other side; anything else goes through the affine forms of the x2 kernel and of the
-        # decoder head (the un-commuted one: 16x the FMAs of the default head).
-        deconv_scale, self.affine = {}, {}
-        for name in ('upscore_conv5', 'upscore'):
-            layer = '%s/%s' % (p, name)
-            if layer + '/gamma' in v:
-                s = v[layer + '/gamma'] / np.sqrt(v[layer + '/moving_variance'] + BN_EPS)
-                t = v[layer + '/beta'] - v[layer + '/moving_mean'] * s
-                if np.all(s > 0) and np.all(np.abs(t) <= 1e-12) and name not in self.dense_deconv:
-                    deconv_scale[name] = s.astype(np.float32)
-                else:
-                    sp, tp = np.ones(self.Up, np.float32), np.zeros(self.Up, np.float32)
-                    sp[:self.U], tp[:self.U] = s, t                  # padding channels: relu(0 * 1 + 0) = 0
-                    self.affine[name] = (torch.from_numpy(sp).to(dev), torch.from_numpy(tp).to(dev))
+            kern = dense_deconv_weights(v['%s/%s/kernel' % (p, name)], stride, self.U, self.Up, dev)
+            if kern is not None:
+                self.dense_deconv[name] = kern
+            scale, affine = deconv_batch_norm(v, '%s/%s' % (p, name), self.U, self.Up, dev, kern is not None)
+            if scale is not None:
+                deconv_scale[name] = scale
+            if affine is not None:
+                self.affine[name] = affine
         self.w, self.b = {}, {}
 
-        def up(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-        for name, cout, _ in ENCODER:
-            k, b = _fold_bn(v, '%s/%s' % (p, name), v['%s/%s/kernel' % (p, name)], v['%s/%s/bias' % (p, name)])
-            self.w[name] = up(k) if name == 'conv1_1' else ops.pack_conv_weights(up(k))
-            self.b[name] = up(b)
-        for name in ('score_conv4', 'score_conv5'):
+        def folded(name):
             k, b = _fold_bn(v, '%s/%s' % (p, name), v['%s/%s/kernel' % (p, name)], v['%s/%s/bias' % (p, name)])
             if name == 'score_conv5' and 'upscore_conv5' in deconv_scale:
                 # s*relu(up2(relu(z))) == relu(up2(relu(s*z))) for s > 0
                 k, b = k * deconv_scale['upscore_conv5'], b * deconv_scale['upscore_conv5']
-            kp = np.zeros((1, 1, 512, self.Up), np.float32)
-            kp[..., :self.U] = k
-            bp = np.zeros(self.Up, np.float32)
-            bp[:self.U] = b
-            self.w[name] = ops.pack_conv_weights(up(kp))
-            self.b[name] = up(bp)
+            return padded_score_conv(k, b, self.U, self.Up) if name.startswith('score_conv') else (k, b)
+
+        for name in [e[0] for e in ENCODER] + ['score_conv4', 'score_conv5']:
+            k, b = folded(name)
+            self.w[name] = upload(k, dev) if name == 'conv1_1' else ops.pack_conv_weights(upload(k, dev))
+            self.b[name] = upload(b, dev)
         k, b = _fold_bn(v, p + '/score', v[p + '/score/kernel'], v[p + '/score/bias'])
         k = k.reshape(self.U, self.C)
         if 'upscore' in deconv_scale:
             k = k * deconv_scale['upscore'][:, None]       # score(s*up) == (s-scaled score weights)(up)
-        ws = np.zeros((self.Up, self.C), np.float32)
-        ws[:self.U] = k
-        self.w['score'] = up(ws)
-        self.b['score'] = up(b)
+        self.w['score'] = padded_score_matrix(k, self.Up, dev)
+        self.b['score'] = upload(b, dev)
         if self.conv_dtype == 'fp8':
             # e4m3 images of the same (batch-norm folded) kernels, each with its own power-of-two scale
             self.w8, self.w8_exp = {}, {}
             for name in ('conv1_2', 'conv2_1') + FP8_CONVS + ('score_conv4', 'score_conv5'):
-                k, _ = _fold_bn(v, '%s/%s' % (p, name), v['%s/%s/kernel' % (p, name)], v['%s/%s/bias' % (p, name)])
-                if name == 'score_conv5' and 'upscore_conv5' in deconv_scale:
-                    k = k * deconv_scale['upscore_conv5']
-                if name.startswith('score_conv'):
-                    kp = np.zeros((1, 1, 512, self.Up), np.float32)
-                    kp[..., :self.U] = k
-                    k = kp
-                self.w8[name], self.w8_exp[name] = ops.pack_conv_weights_f8(up(k))
+                self.w8[name], self.w8_exp[name] = ops.pack_conv_weights_f8(upload(folded(name)[0], dev))
         torch.cuda.synchronize(dev)
-
-    def _sk(self):
-        """This engine's stream-K workspace (ops.streamk_workspace: arrival counters + partial-tile slabs of the
-        generation-2 conv kernel's tail round).  One per engine: the two experts of a fusion model run on two streams."""
-        if not self.streamk:
-            return None
-        ws = self._arena.get('streamk_ws')
-        if ws is None:
-            ws = self._arena['streamk_ws'] = ops.streamk_workspace(self.device)
-        return ws
-
-    # ---- activations ---------------------------------------------------------------------------
-    def _act(self, name, n, h, w, c, dtype='bf16', scale_exp=0):
-        key = (name, n, h, w, c, dtype)
-        a = self._arena.get(key)
-        if a is None:
-            a = ops.Act(n, h, w, c, self.device, dtype=dtype, scale_exp=scale_exp)
-            self._arena[key] = a
-        elif a.scale_exp != scale_exp:
-            a.set_scale_exp(scale_exp)
-        return a
 
     # ---- fp8: static per-tensor scales -----------------------------------------------------------------------
     def calibrate(self, x, margin_bits=1, _implicit=False, method=None):
@@ -353,54 +525,12 @@ class FcnEngine(object):
         self.fp8_guard = {'chosen': chosen, 'agreement': {k: round(v, 6) for k, v in report.items()}, 'bound': float(agreement)}
         return scales
 
-    def _encoder_fp8(self, x, keep_all=False):
-        """The trunk with e4m3 operands from conv2_1 / conv2_2 on (see fp8_plan); same layer dict as `encoder`."""
+    def _fp8_plan(self, x):
+        if self.conv_dtype != 'fp8' or self.fp8_off:
+            return (), ()
         if self.fp8_scales is None:
             self.calibrate(x, _implicit=True)           # first batch seen = calibration batch
-        n, h, w, _ = x.shape
-        e = self.fp8_scales
-        convs8, maps8 = fp8_plan(h, w, self.fp8_deep, self.fp8_start)
-        L = {}
-        first = 1
-        ch, cw = h, w
-        # conv1_1 + conv1_2 + pool1 in one launch straight onto the first e4m3 map (csrc/conv_first_fused.hip, its e4m3-out form:
-        # the same bytes as the two kernels) where conv1_2 takes bf16 operands (the default plan) and neither full map is wanted
-        if not keep_all and 'conv1_1' not in maps8 and 'conv1_2' not in convs8 and \
-                ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
-            # (fp8_start behind conv2_1: pool1 stays bf16)
-            q = self._act('pool1', n, h // 2, w // 2, 64, **(dict(dtype='fp8', scale_exp=e['conv1_2']) if 'conv1_2' in maps8 else {}))
-            if ops.conv_first_pair_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], self.w['conv1_2'],
-                                       self.b['conv1_2'], pooled=q):
-                L['pool1'] = cur = q
-                ch, cw = h // 2, w // 2
-                first = 2
-        if first == 1:
-            cur = self._act('conv1_1', n, h, w, 64, **(dict(dtype='fp8', scale_exp=e['conv1_1']) if 'conv1_1' in maps8 else {}))
-            ops.conv2d_first_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], cur, relu=True)
-            L['conv1_1'] = cur
-        for name, cout, pool in ENCODER[first:]:
-            f8_in = name in convs8
-            f8_out = name in maps8
-            wts = self.w8[name] if f8_in else self.w[name]
-            kw = dict(dtype='fp8', scale_exp=e[name]) if f8_out else {}
-            if pool is None:
-                y = self._act(name, n, ch, cw, cout, **kw)
-                ops.conv2d_fwd(cur, wts, self.b[name], 3, relu=True, y=y)
-                L[name] = cur = y
-            else:
-                q = self._act(pool, n, ch // 2, cw // 2, cout, **kw)
-                need_full = keep_all or name == 'conv4_3'
-                y = self._act(name, n, ch, cw, cout, **kw) if need_full else None
-                ops.conv2d_fwd(cur, wts, self.b[name], 3, relu=True, y=y, pooled=q, write_y=need_full)
-                if y is not None:
-                    L[name] = y
-                L[pool] = cur = q
-                ch, cw = ch // 2, cw // 2
-        s4 = self._act('score_conv4', n, h // 8, w // 8, self.Up)
-        ops.conv2d_fwd(L['conv4_3'], self.w8['score_conv4'], self.b['score_conv4'], 1, relu=True, y=s4)
-        s5 = self._act('score_conv5', n, h // 16, w // 16, self.Up)
-        ops.conv2d_fwd(L['conv5_3'], self.w8['score_conv5'], self.b['score_conv5'], 1, relu=True, y=s5)
-        return L, s4, s5
+        return fp8_plan(x.shape[1], x.shape[2], self.fp8_deep, self.fp8_start)
 
     def encoder(self, x, keep_all=False, routed=False):
         """x: float32 [N,H,W,cin] device tensor (raw 0..255 RGB / raw depth, data contract of
@@ -411,88 +541,10 @@ class FcnEngine(object):
         takes the shape."""
         return self.encoder_finish(self.encoder_begin(x, keep_all=keep_all, stop=len(ENCODER), routed=routed))
 
-    # The encoder in three steps, so that a fusion model can run the layers its two experts share as ONE launch each
-    # (encoder_layers_pair below): encoder_begin (input checks, the first conv(s), the layers before `stop`), the remaining
-    # layers (here or paired), encoder_finish (score convs, x2 upsampling + skip).
-    def encoder_begin(self, x, keep_all=False, stop=None, routed=False):
-        n, h, w, cin = x.shape
-        if cin != self.cin:
-            raise ValueError('expected %d input channels, got %d' % (self.cin, cin))
-        if h % 16 or w % 16:
-            raise ValueError('H and W must be multiples of 16 (augmentation.py:244-262 crop_multiple)')
-        st = {'n': n, 'h': h, 'w': w, 'keep_all': keep_all, 'routed': bool(routed) and keep_all}
-        if self.conv_dtype == 'fp8' and not self.fp8_off:
-            st['L'], st['s4'], st['s5'] = self._encoder_fp8(x, keep_all)
-            st['next'] = len(ENCODER)
-            return st
-        L = {}
-        ch, cw = h, w
-        first = 1
-        # conv1_1 + conv1_2 + pool1 in one launch where neither full-resolution map is wanted (inference): conv1_1 is
-        # evaluated straight into conv1_2's LDS patch buffers (csrc/conv_first_fused.hip; the same bits as the two
-        # kernels).  Maps that do not tile in 16x32 take the two kernels.
-        if not keep_all and ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
-            q = self._act('pool1', n, h // 2, w // 2, 64)
-            if ops.conv_first_pair_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], self.w['conv1_2'],
-                                       self.b['conv1_2'], pooled=q):
-                L['pool1'] = cur = q
-                ch, cw = h // 2, w // 2
-                first = 2
-        if first == 1:
-            cur = self._act('conv1_1', n, h, w, 64)
-            ops.conv2d_first_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], cur, relu=True)
-            L['conv1_1'] = cur
-        st.update(L=L, cur=cur, ch=ch, cw=cw, next=first)
-        self.encoder_layers(st, len(ENCODER) if stop is None else stop)
-        return st
-
+    # The encoder in three steps (Vgg16Walk.encoder_begin, the remaining layers here or paired: encoder_layers_pair, and
+    # encoder_finish: score convs, x2 upsampling + skip).
     def _drop_fn(self):
         return self._dropout if self.dropout_layers and self.dropout_rate > 0 else None
-
-    def _layer_outputs(self, st, idx):
-        """(full map or None, pooled map or None) of encoder layer idx"""
-        name, cout, pool = ENCODER[idx]
-        n, ch, cw = st['n'], st['ch'], st['cw']
-        if pool is None:
-            return self._act(name, n, ch, cw, cout), None
-        need_full = st['keep_all'] or name == 'conv4_3'       # conv4_3 feeds score_conv4
-        return (self._act(name, n, ch, cw, cout) if need_full else None), self._act(pool, n, ch // 2, cw // 2, cout)
-
-    def _layer_done(self, st, idx, y, q):
-        name, cout, pool = ENCODER[idx]
-        L = st['L']
-        if pool is None:
-            L[name] = st['cur'] = y
-        else:
-            if y is not None:
-                L[name] = y
-            L[pool] = st['cur'] = q
-            st['ch'], st['cw'] = st['ch'] // 2, st['cw'] // 2
-            # simple_fcn.py:51-63: the dropout after pool4 is gated by 'pool3' too (a quirk of the reference:
-            # 'pool4' alone enables nothing)
-            drop = self._drop_fn()
-            if drop is not None and pool in ('pool3', 'pool4') and 'pool3' in self.dropout_layers:
-                L[pool + '_drop'] = st['cur'] = drop(q, pool + '_drop')
-        st['next'] = idx + 1
-
-    def encoder_layers(self, st, stop):
-        """encoder layers [st['next'], stop), one launch each"""
-        for idx in range(st['next'], stop):
-            name = ENCODER[idx][0]
-            y, q = self._layer_outputs(st, idx)
-            if st.get('routed') and q is not None and name != 'conv4_3' and self._drop_fn() is None:
-                key = ('route_' + name, st['n'], q.h, q.w, q.c)
-                route = self._arena.get(key)
-                if route is None:
-                    route = self._arena[key] = torch.empty(st['n'] * q.h * q.w * q.c, dtype=torch.uint8, device=self.device)
-                if ops.conv2d_fwd_route(st['cur'], self.w[name], self.b[name], q, route):
-                    st['L']['route_' + name] = route
-                    self._layer_done(st, idx, None, q)
-                    continue
-            ops.conv2d_fwd(st['cur'], self.w[name], self.b[name], 3, relu=True, y=y, pooled=q, write_y=y is not None,
-                           workspace=self._sk(),
-                           split_ws=ops.split_workspace(st['cur'], ENCODER[idx][1], self._arena) if q is None else None)
-            self._layer_done(st, idx, y, q)
 
     def pairable(self):
         """May this engine's 3x3 layers share launches with a twin's (encoder_layers_pair)?"""
@@ -505,21 +557,16 @@ class FcnEngine(object):
             s4, s5 = st['s4'], st['s5']
         else:
             self.encoder_layers(st, len(ENCODER))
-            drop = self._drop_fn()
+            drop = self._drop_fn()                        # (sites exist in the bf16 graph only: set_dropout)
+            wts = self.w8 if st['convs8'] else self.w     # an fp8 plan ends in e4m3 conv4_3 / conv5_3 maps (fp8_plan)
             s4 = self._act('score_conv4', n, h // 8, w // 8, self.Up)
             c43 = drop(L['conv4_3'], 'conv4_3_drop') if drop is not None and 'conv4_3' in self.dropout_layers else L['conv4_3']
-            ops.conv2d_fwd(c43, self.w['score_conv4'], self.b['score_conv4'], 1, relu=True, y=s4)
+            ops.conv2d_fwd(c43, wts['score_conv4'], self.b['score_conv4'], 1, relu=True, y=s4)
             s5 = self._act('score_conv5', n, h // 16, w // 16, self.Up)
             c53 = drop(L['conv5_3'], 'conv5_3_drop') if drop is not None and 'conv5_3' in self.dropout_layers else L['conv5_3']
-            ops.conv2d_fwd(c53, self.w['score_conv5'], self.b['score_conv5'], 1, relu=True, y=s5)
-        fused = self._act('fused', n, h // 8, w // 8, self.Up)
-        aff = self.affine.get('upscore_conv5', (None, None))
-        if 'upscore_conv5' in self.dense_deconv:
-            wk, zb = self.dense_deconv['upscore_conv5']
-            _, self._arena['dd_ws5'] = ops.deconv_dense_fwd(s5, wk, zb, 2, self.Up, y=fused, scale=aff[0], shift=aff[1],
-                                                           residual=s4, relu=True, workspace=self._arena.get('dd_ws5'))
-        else:
-            ops.upsample2x_relu_add(s5, residual=s4, y=fused, scale=aff[0], shift=aff[1])
+            ops.conv2d_fwd(c53, wts['score_conv5'], self.b['score_conv5'], 1, relu=True, y=s5)
+        fused = upsample2x_skip(self, s5, s4, self._act('fused', n, h // 8, w // 8, self.Up),
+                                self.dense_deconv.get('upscore_conv5'), self.affine.get('upscore_conv5'))
         L.update(score_conv4=s4, score_conv5=s5, fused=fused)
         if self.dropout_rate > 0 and 'features' in self.dropout_layers:
             # decoder(..., dropout_rate) drops its input features INSIDE the decoder (simple_fcn.py:124-126): the layer
@@ -577,8 +624,7 @@ class FcnEngine(object):
             m = (k + 1) * n
             rep = self._act('pool3_mc', m, pool3.h, pool3.w, pool3.c)
             ops.dropout_samples(pool3, k, rate, self._dropout_seed_of(seed, p0 + a, 'pool3_drop'), 1000003, y=rep)
-            sc = {'n': m, 'h': h, 'w': w, 'keep_all': False, 'routed': False, 'L': {}, 'cur': rep, 'ch': pool3.h,
-                  'cw': pool3.w, 'next': i41}
+            sc = self._state(m, h, w, cur=rep, next=i41)
             self.encoder_layers(sc, i43 + 1)
             ops.dropout_samples(sc['cur'], k, rate, self._dropout_seed_of(seed, p0 + a, 'pool4_drop'), 1000003, in_place=True)
             f = self.encoder_finish(sc)['fused']
@@ -716,8 +762,7 @@ class FcnEngine(object):
                 return y
 
             if pool:
-                sc = {'n': m, 'h': h, 'w': w, 'keep_all': False, 'routed': False, 'L': {}, 'ch': st['ch'], 'cw': st['cw'],
-                      'cur': slots(st['cur'], 'pool3', True), 'next': i41}
+                sc = self._state(m, h, w, cur=slots(st['cur'], 'pool3', True), next=i41)
                 self.encoder_layers(sc, i43 + 1)
                 drop(sc['cur'], 'pool4')
                 self.encoder_layers(sc, len(ENCODER))
@@ -775,32 +820,7 @@ class FcnEngine(object):
             ws = torch.empty(ops._lib.lib().xv_decoder_head_workspace_bytes(f.n, f.h, f.w, self.C) // 4,
                              dtype=torch.float32, device=self.device)
             self._arena[key] = ws
-        aff = self.affine.get('upscore', (None, None))
-        if 'upscore' in self.dense_deconv:
-            # dense x8 deconv -> [batch norm] -> relu at full resolution, then the per-pixel score conv, softmax, argmax
-            wk, zb = self.dense_deconv['upscore']
-            up = self._act('upscore', f.n, 8 * f.h, 8 * f.w, self.Up)
-            _, self._arena['dd_ws'] = ops.deconv_dense_fwd(f, wk, zb, 8, self.Up, y=up, scale=aff[0], shift=aff[1],
-                                                          relu=True, workspace=self._arena.get('dd_ws'))
-            skey = ('dense_score', f.n, f.h, f.w)
-            if skey not in self._arena:
-                self._arena[skey] = torch.empty((f.n, 8 * f.h, 8 * f.w, self.C), dtype=torch.float32, device=self.device)
-            score = ops.score_dense_fwd(up, self.w['score'], self.b['score'], self.C, self._arena[skey])
-            want_label = 'label' in want or 'classification' in want
-            prob, label = ops.softmax_argmax(score, want_prob='prob' in want, want_label=want_label)
-            out = {'layers': L}
-            L['upscore'] = up
-            if 'score' in want:
-                out['score'] = score
-            if prob is not None:
-                out['prob'] = prob
-            if label is not None:
-                out['label'] = out['classification'] = label
-            return out
-        out = ops.decoder_head_fwd(f, self.w['score'], self.b['score'], self.C,
-                                   want_score='score' in want, want_prob='prob' in want,
-                                   want_label=('label' in want or 'classification' in want), workspace=ws,
-                                   scale=aff[0], shift=aff[1])
+        out = decoder_head(self, f, want, self.dense_deconv.get('upscore'), self.affine.get('upscore'), L, workspace=ws)
         if 'label' in out:
             out['classification'] = out['label']
         out['layers'] = L

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib, ops
 from .custom_layers import is_bilinear_filter
-from .fcn import BN_EPS, ENCODER, _fold_bn, variable_shapes
+from .fcn import BN_EPS, ENCODER, _fold_bn, check_variables, variable_shapes
 
 
 # True: round 4's vector-ALU conv kernel + stand-alone pools (the A/B baseline of the bench record sets it)
@@ -37,11 +37,8 @@ class FcnEngineF32(object):
     def load(self, variables):
         p, dev = self.prefix, self.device
         v = {k: np.asarray(a, np.float32) for k, a in variables.items() if k.startswith(p + '/')}
-        for need, shape in variable_shapes(p, self.cin, self.U, self.C).items():
-            if need not in v:
-                raise KeyError('missing variable %s' % need)
-            if tuple(v[need].shape) != tuple(shape):
-                raise ValueError('variable %s has shape %s, expected %s' % (need, v[need].shape, shape))
+        check_variables(v, variable_shapes(p, self.cin, self.U, self.C))
+
         def up(a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 

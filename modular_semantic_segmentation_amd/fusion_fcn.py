@@ -15,8 +15,9 @@ import torch
 
 from . import ops
 from .base_model import BaseModel
-from .custom_layers import bilinear_filter, dense_deconv_as_conv3x3, is_bilinear_filter
-from .fcn import BN_EPS, ENCODER, _fold_bn, padded_units
+from .custom_layers import bilinear_filter
+from .fcn import (ENCODER, Arena, Vgg16Walk, _fold_bn, check_variables, decoder_head, deconv_batch_norm, dense_deconv_weights,
+                  padded_score_conv, padded_score_matrix, padded_units, upload, upsample2x_skip)
 
 
 def vgg16_variable_shapes(prefix, in_channels):
@@ -69,8 +70,10 @@ def init_variables(prefixes, num_channels, num_units, num_classes, seed=None):
     return out
 
 
-class VggTrunk(object):
-    """vgg16() for one modality: 13 convs, pool1..pool4 fused into the conv epilogues."""
+class VggTrunk(Vgg16Walk):
+    """vgg16() for one modality: 13 convs, pool1..pool4 fused into the conv epilogues (fcn.Vgg16Walk, the walk of the FCN
+    experts, in bf16 and without its stream-K option)."""
+    split_small = False     # the joint model never had the split form; whether it gains from it is unmeasured
 
     def __init__(self, prefix, in_channels, variables, device):
         self.prefix, self.cin, self.device = prefix, int(in_channels), torch.device(device)
@@ -79,81 +82,24 @@ class VggTrunk(object):
 
     def load(self, variables):
         self.w, self.b = {}, {}
-        for name, shape in vgg16_variable_shapes(self.prefix, self.cin).items():
-            if name not in variables:
-                raise KeyError('missing variable %s' % name)
-            if tuple(np.shape(variables[name])) != tuple(shape):
-                raise ValueError('variable %s has shape %s, expected %s' % (name, np.shape(variables[name]), shape))
-
-        def up(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
-
+        check_variables(variables, vgg16_variable_shapes(self.prefix, self.cin))
         for name, _, _ in ENCODER:
             layer = '%s_%s' % (self.prefix, name)
             k, b = _fold_bn(variables, layer, np.asarray(variables[layer + '/kernel'], np.float32),
                             np.asarray(variables[layer + '/bias'], np.float32))
-            self.w[name] = up(k) if name == 'conv1_1' else ops.pack_conv_weights(up(k))
-            self.b[name] = up(b)
-
-    def _act(self, name, n, h, w, c):
-        key = (name, n, h, w, c)
-        a = self._arena.get(key)
-        if a is None:
-            a = self._arena[key] = ops.Act(n, h, w, c, self.device)
-        return a
+            k = upload(k, self.device)
+            self.w[name] = k if name == 'conv1_1' else ops.pack_conv_weights(k)
+            self.b[name] = upload(b, self.device)
 
     def forward(self, x, keep_all=False, routed=False):
-        """x: float32 [N,H,W,cin] device tensor -> dict of Acts (always 'conv4_3', 'conv5_3').  As FcnEngine.encoder:
+        """x: float32 [N,H,W,cin] device tensor -> dict of Acts (always 'conv4_3', 'conv5_3'), as FcnEngine.encoder's:
         without keep_all, conv1_1 + conv1_2 + pool1 are one launch (ops.conv_first_pair_fwd: neither full-resolution map is
         written); routed=True (with keep_all: the training step) leaves out the full map of a conv in front of a pool, whose
         only reader would be MaxPoolGrad, and keeps the pool's route bytes ('route_<conv>') for the data-gradient conv."""
-        n, h, w, cin = x.shape
-        if cin != self.cin:
-            raise ValueError('expected %d input channels, got %d' % (self.cin, cin))
-        if h % 16 or w % 16:
-            raise ValueError('H and W must be multiples of 16')
-        L = {}
-        ch, cw = h, w
-        first = 1
-        if not keep_all and ENCODER[1][0] == 'conv1_2' and ENCODER[1][2] == 'pool1':
-            q = self._act('pool1', n, h // 2, w // 2, 64)
-            if ops.conv_first_pair_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], self.w['conv1_2'], self.b['conv1_2'],
-                                       pooled=q):
-                L['pool1'] = cur = q
-                ch, cw = h // 2, w // 2
-                first = 2
-        if first == 1:
-            cur = self._act('conv1_1', n, h, w, 64)
-            ops.conv2d_first_fwd(x.contiguous(), self.w['conv1_1'], self.b['conv1_1'], cur, relu=True)
-            L['conv1_1'] = cur
-        for name, cout, pool in ENCODER[first:]:
-            if pool is None:
-                y = self._act(name, n, ch, cw, cout)
-                ops.conv2d_fwd(cur, self.w[name], self.b[name], 3, relu=True, y=y)
-                L[name] = cur = y
-            else:
-                q = self._act(pool, n, ch // 2, cw // 2, cout)
-                if routed and keep_all and name != 'conv4_3':
-                    key = ('route_' + name, n, q.h, q.w, q.c)
-                    route = self._arena.get(key)
-                    if route is None:
-                        route = self._arena[key] = torch.empty(n * q.h * q.w * q.c, dtype=torch.uint8, device=self.device)
-                    if ops.conv2d_fwd_route(cur, self.w[name], self.b[name], q, route):
-                        L['route_' + name] = route
-                        L[pool] = cur = q
-                        ch, cw = ch // 2, cw // 2
-                        continue
-                need_full = keep_all or name == 'conv4_3'
-                y = self._act(name, n, ch, cw, cout) if need_full else None
-                ops.conv2d_fwd(cur, self.w[name], self.b[name], 3, relu=True, y=y, pooled=q, write_y=need_full)
-                if y is not None:
-                    L[name] = y
-                L[pool] = cur = q
-                ch, cw = ch // 2, cw // 2
-        return L
+        return self.encoder_begin(x, keep_all=keep_all, routed=routed)['L']
 
 
-class FusionFcnEngine(object):
+class FusionFcnEngine(Arena):
     """The whole fusion_fcn() inference graph resident on one GPU."""
 
     def __init__(self, prefixes, num_channels, num_units, num_classes, variables, device='cuda'):
@@ -170,69 +116,32 @@ class FusionFcnEngine(object):
         v = {k: np.asarray(a, np.float32) for k, a in variables.items()}
         dev = self.device
         has_bn = 'fused/upscore/gamma' in v
-        for need, shape in variable_shapes(self.prefixes, self.num_channels, self.U, self.C, has_bn).items():
-            if need not in v:
-                raise KeyError('missing variable %s' % need)
-            if tuple(v[need].shape) != tuple(shape):
-                raise ValueError('variable %s has shape %s, expected %s' % (need, v[need].shape, shape))
-        # The reference never trains its deconvs (fusion_fcn.py:26-31: trainable=False), so their kernels are the bilinear
-        # constant and run as depthwise interpolations.  An imported kernel that is anything else takes the dense
-        # transposed-conv path, as in fcn.FcnEngine (xv_deconv_dense_fwd on the MFMA conv; the decoder head is then the
-        # un-commuted one: dense x8 deconv -> [batch norm] -> relu, per-pixel score conv, softmax, argmax).
+        check_variables(v, variable_shapes(self.prefixes, self.num_channels, self.U, self.C, has_bn))
         self.dense_deconv = {}
         for name, stride in (('fused_upscore_conv5', 2), ('fused/upscore', 8)):
-            kern = v[name + '/kernel']
-            if not is_bilinear_filter(kern):
-                kp = np.zeros((kern.shape[0], kern.shape[1], self.Up, self.Up), np.float32)
-                kp[:, :, :self.U, :self.U] = kern                       # padding units: zero rows and columns
-                k3 = torch.from_numpy(dense_deconv_as_conv3x3(kp, stride)).to(dev)
-                self.dense_deconv[name] = (ops.pack_conv_weights(k3),
-                                           torch.zeros(stride * stride * self.Up, dtype=torch.float32, device=dev))
+            kern = dense_deconv_weights(v[name + '/kernel'], stride, self.U, self.Up, dev)
+            if kern is not None:
+                self.dense_deconv[name] = kern
         for m, prefix in self.prefixes.items():
             if m in self.trunks:
                 self.trunks[m].load(v)
             else:
                 self.trunks[m] = VggTrunk(prefix, self.num_channels[m], v, dev)
-
-        def up(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
         self.w, self.b = {}, {}
-        e = len(self.prefixes)
         for name in ('fused_score_conv4', 'fused_score_conv5'):
-            k, b = _fold_bn(v, name, v[name + '/kernel'], v[name + '/bias'])
-            kp = np.zeros((1, 1, 512 * e, self.Up), np.float32)
-            kp[..., :self.U] = k
-            bp = np.zeros(self.Up, np.float32)
-            bp[:self.U] = b
-            self.w[name] = ops.pack_conv_weights(up(kp))
-            self.b[name] = up(bp)
+            kp, bp = padded_score_conv(*_fold_bn(v, name, v[name + '/kernel'], v[name + '/bias']), self.U, self.Up)
+            self.w[name] = ops.pack_conv_weights(upload(kp, dev))
+            self.b[name] = upload(bp, dev)
         # decoder: BN on the 1x1 score conv (no activation) folds exactly; BN between the x8 deconv and its relu is
         # folded when scale-only, else handed to the general decoder head as a per-channel affine
         k, b = _fold_bn(v, 'fused/score', v['fused/score/kernel'], v['fused/score/bias'])
         k = k.reshape(self.U, self.C)
-        self.head_affine = None
-        if has_bn:
-            s = v['fused/upscore/gamma'] / np.sqrt(v['fused/upscore/moving_variance'] + BN_EPS)
-            t = v['fused/upscore/beta'] - v['fused/upscore/moving_mean'] * s
-            if np.all(s > 0) and np.all(np.abs(t) <= 1e-12) and 'fused/upscore' not in self.dense_deconv:
-                k = k * s[:, None]
-            else:
-                sp, tp = np.ones(self.Up, np.float32), np.zeros(self.Up, np.float32)
-                sp[:self.U], tp[:self.U] = s, t
-                self.head_affine = (up(sp), up(tp))
-        ws = np.zeros((self.Up, self.C), np.float32)
-        ws[:self.U] = k
-        self.w['score'] = up(ws)
-        self.b['score'] = up(b)
+        scale, self.head_affine = deconv_batch_norm(v, 'fused/upscore', self.U, self.Up, dev, 'fused/upscore' in self.dense_deconv)
+        if scale is not None:
+            k = k * scale[:, None]
+        self.w['score'] = padded_score_matrix(k, self.Up, dev)
+        self.b['score'] = upload(b, dev)
         torch.cuda.synchronize(dev)
-
-    def _act(self, name, n, h, w, c):
-        key = (name, n, h, w, c)
-        a = self._arena.get(key)
-        if a is None:
-            a = self._arena[key] = ops.Act(n, h, w, c, self.device)
-        return a
 
     def forward(self, inputs, want=('label',), keep_all=False):
         """inputs: {modality: float32 [N,H,W,c] device tensor}.  Returns dict with any of 'score', 'prob',
@@ -272,37 +181,10 @@ class FusionFcnEngine(object):
         ops.conv2d_fwd(c4, self.w['fused_score_conv4'], self.b['fused_score_conv4'], 1, relu=True, y=s4)
         s5 = self._act('score_conv5', n, h8 // 2, w8 // 2, self.Up)
         ops.conv2d_fwd(c5, self.w['fused_score_conv5'], self.b['fused_score_conv5'], 1, relu=True, y=s5)
-        feat = self._act('features', n, h8, w8, self.Up)
-        if 'fused_upscore_conv5' in self.dense_deconv:
-            wk, zb = self.dense_deconv['fused_upscore_conv5']
-            _, self._arena['dd_ws5'] = ops.deconv_dense_fwd(s5, wk, zb, 2, self.Up, y=feat, residual=s4, relu=True,
-                                                           workspace=self._arena.get('dd_ws5'))
-        else:
-            ops.upsample2x_relu_add(s5, residual=s4, y=feat)
-        aff = self.head_affine or (None, None)
-        want_label = 'label' in want or 'classification' in want
+        feat = upsample2x_skip(self, s5, s4, self._act('features', n, h8, w8, self.Up),
+                               self.dense_deconv.get('fused_upscore_conv5'), None)
         layers.update(concat_conv4=c4, concat_conv5=c5, score_conv4=s4, score_conv5=s5, features=feat)
-        if 'fused/upscore' in self.dense_deconv:
-            wk, zb = self.dense_deconv['fused/upscore']
-            up = self._act('upscore', n, 8 * h8, 8 * w8, self.Up)
-            _, self._arena['dd_ws'] = ops.deconv_dense_fwd(feat, wk, zb, 8, self.Up, y=up, scale=aff[0], shift=aff[1],
-                                                          relu=True, workspace=self._arena.get('dd_ws'))
-            skey = ('dense_score', n, h8, w8)
-            if skey not in self._arena:
-                self._arena[skey] = torch.empty((n, 8 * h8, 8 * w8, self.C), dtype=torch.float32, device=self.device)
-            score = ops.score_dense_fwd(up, self.w['score'], self.b['score'], self.C, self._arena[skey])
-            prob, label = ops.softmax_argmax(score, want_prob='prob' in want, want_label=want_label)
-            out = {}
-            layers['upscore'] = up
-            if 'score' in want:
-                out['score'] = score
-            if prob is not None:
-                out['prob'] = prob
-            if label is not None:
-                out['label'] = label
-        else:
-            out = ops.decoder_head_fwd(feat, self.w['score'], self.b['score'], self.C, want_score='score' in want,
-                                       want_prob='prob' in want, want_label=want_label, scale=aff[0], shift=aff[1])
+        out = decoder_head(self, feat, want, self.dense_deconv.get('fused/upscore'), self.head_affine, layers)
         out['layers'] = layers
         return out
 
