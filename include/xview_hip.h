@@ -529,6 +529,22 @@ int xv_fused_head_joint_hist_grouped_fwd(const float* Sa, const float* Sb, const
 int xv_fused_head_average_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n, int hi,
                               int wi, int num_classes, int64_t* fused_label, void* stream);
 
+/* Fused head of a fusion model with TWO TO FOUR experts: S and bias are host arrays of num_experts device pointers (as
+ * xv_bayes_fuse takes `labels`), S[e] float32 [n][hi+2][wi+2][CP] from xv_score_lowres of expert e (16-byte aligned), bias[e]
+ * float32 [C]; the pointers travel in the kernel arguments, nothing is staged in device memory.  Per output pixel every
+ * expert's softmax / argmax (bits of xv_decoder_head_fwd's prob / label), the experts in ascending order, then
+ *   mode 0, Bayes:     tab = loglik float32 [E][C][C], logprior [C]: the label of xv_bayes_fuse on the E label maps;
+ *   mode 1, Dirichlet: tab = alpha - 1 float32 [E][C][C], lognorm [E][C], logprior [C]: the label of xv_dirichlet_fuse on
+ *                      the E probability maps;
+ *   mode 2, mean:      tab, lognorm, logprior ignored (may be NULL): the label of xv_average_fuse on the E probability maps
+ * -> fused_label int64 [n][8hi][8wi] (16-byte aligned), bit for bit, without the E label or probability maps.  For two
+ * experts the labels are those of xv_fused_head_fwd / xv_fused_head_average_fwd.  XV_EINVAL, with nothing launched and the
+ * output untouched, for num_experts outside 2..4, num_classes outside 2..32, an unknown mode, non-positive sizes, or a null
+ * or misaligned pointer the mode needs.                                                                                      */
+int xv_fused_head_multi_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                            int num_classes, int mode, const float* tab, const float* lognorm, const float* logprior,
+                            int64_t* fused_label, void* stream);
+
 /* Counting form of the fused average head: cm int64 [C][C] (rows = ground truth), cm[label][fused] += 1 over the pixels with
  * 0 <= label < C (labels int32 [n][8hi][8wi], 16-byte aligned) as xv_confusion_matrix would count xv_fused_head_average_fwd's
  * labels: accumulated, not cleared; no label map is written.  max_workgroups bounds the grid (0: the kernel's own bound).

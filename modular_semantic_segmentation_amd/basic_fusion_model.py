@@ -186,6 +186,29 @@ def fused_head_applicable(model):
     return all(isinstance(e, FcnEngine) and e.commuted_head() for e in model.experts.values())
 
 
+MULTI_HEAD_EXPERTS = (3, 4)         # xv_fused_head_multi_fwd takes two to four; two experts keep the two-expert heads
+
+
+def multi_head_applicable(model):
+    """The fused head for three or four experts (ops.fused_head_multi) serves the default prediction of a fusion model with
+    that many FCN experts whose decoder heads are in the commuted form; config fused_head=False keeps the per-expert outputs
+    materialised.  Two experts are fused_head_applicable's; five or more fuse materialised outputs."""
+    if not model.config.get('fused_head', True) or len(model.modalities) not in MULTI_HEAD_EXPERTS:
+        return False
+    return all(isinstance(e, FcnEngine) and e.commuted_head() for e in model.experts.values())
+
+
+def run_lowres_scores_multi(model, batch):
+    """Every trunk on its own stream (run_trunks without a paired section) up to its low-resolution class scores:
+    (scores, biases, n, hi, wi) with one entry per modality, in the model's order -- what ops.fused_head_multi takes."""
+    inputs = {m: model._to_device(batch[m], torch.float32) for m in model.modalities}
+    res = run_trunks(model, inputs, lambda m, st: model.experts[m].lowres_scores(inputs[m], st=st), pair=False)
+    n, hi, wi = res[model.modalities[0]][1]
+    if any(res[m][1] != (n, hi, wi) for m in model.modalities):
+        raise ValueError('the experts disagree on the size of their low-resolution scores: %s' % {m: res[m][1] for m in model.modalities})
+    return ([res[m][0] for m in model.modalities], [model.experts[m].b['score'] for m in model.modalities], n, hi, wi)
+
+
 def _head_arguments(model, res):
     """(Sa, Sb, bias_a, bias_b, n, hi, wi), what the two-expert heads take, from {modality: (scores, (n, hi, wi))}."""
     a, b = model.modalities
@@ -363,6 +386,11 @@ class FusionModel(BaseModel):
         labels in ONE kernel, per-expert softmax / argmax included -- or None: it fuses materialised expert outputs only."""
         return None
 
+    def _multi_head(self):
+        """The model's head for three or four experts' low-resolution scores -- head(scores, biases, n, hi, wi) -> fused
+        labels in ONE kernel (ops.fused_head_multi) -- or None: it fuses materialised expert outputs only."""
+        return None
+
     def _build_experts(self):
         """Hook: fills self.experts {modality: engine} and self.variables (a test without a GPU overrides it)."""
         engine_cls, init = expert_factory(self.config['expert_model'], self.config.get('conv_dtype', 'bf16'))
@@ -403,6 +431,11 @@ class FusionModel(BaseModel):
             # labels and probabilities never leave its registers
             self.expert_outputs = None
             return head(*run_lowres_scores(self, batch))
+        head = self._multi_head() if output_attr is None else None
+        if head is not None and multi_head_applicable(self):
+            # the same for three or four experts: every trunk on its own stream, then one head kernel for all of them
+            self.expert_outputs = None
+            return head(*run_lowres_scores_multi(self, batch))
         key = output_key(output_attr)
         wants = self.expert_wants
         if key == 'probs' and 'prob' not in wants:

@@ -124,6 +124,12 @@ class BayesFusion(FusionModel):
             return None             # the lookup table takes the experts' materialised label maps
         return lambda *scores: ops.fused_head(*scores, self.config['num_classes'], self.loglik, self.logprior)
 
+    def _multi_head(self):
+        if self.config.get('decision_matrix', False):
+            return None             # as _fused_head: that configuration fuses the experts' materialised label maps
+        return lambda *scores: ops.fused_head_multi(*scores, self.config['num_classes'], 'bayes', tab=self.loglik,
+                                                    logprior=self.logprior)
+
     def _fusion(self, expert_outputs, output_attr=None):
         labels = [expert_outputs[m]['classification'] for m in self.modalities]
         want_score = output_attr == 'fused_score'

@@ -1139,6 +1139,260 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 
   }
 }
 
+// ---- fused head for two to four experts (bayes_mix.py:33-58, dirichlet_mix.py:14-36,96-136, average_mix.py:18-21) ------------
+// fused_head_kernel / fused_head_average_kernel generalised from two experts to E = 2 .. 4: per output pixel and expert
+// head_load_taps / head_eval_taps / head_max, then head_label_fast + head_softmax (MODE 0) or head_softmax (MODE 1, 2) -- each
+// expert's label / probabilities with the bits decoder_head_kernel stores -- then the statements of fusion.hip's kernels, the
+// experts in ascending order:
+//   MODE 0, Bayes      score[k] = ((tab_0[l_0][k] + tab_1[l_1][k]) + ...) + logprior[k]            (bayes_fuse_kernel)
+//   MODE 1, Dirichlet  renormalise, log(1e-20 + p), the C fmaf chains over k, - lognorm; total = L_0, total += L_1, ...;
+//                      + logprior                                                                   (dirichlet_fuse_kernel)
+//   MODE 2, mean       s = ((p_0 + p_1) + ...), v = s / E (an IEEE division)                        (average_fuse_kernel)
+// and the first maximum.  The labels are those of E decoder heads + xv_bayes_fuse / xv_dirichlet_fuse / xv_average_fuse bit for
+// bit; the E label maps or probability maps between them never exist.  The experts are worked one after another in a loop
+// that is NOT unrolled into the running registers (Bayes: the labels of a pixel packed into one word; Dirichlet: total [CM];
+// mean: s [P][CM]): nothing of size E * C is held, and the register count is the two-expert sibling's whatever E is.  The score
+// and bias pointers are kernel arguments (HeadPtrs, as LabelPtrs / ProbPtrs in fusion.hip): no pointer table in device
+// memory, a captured graph of the step stays valid.
+// Pixels per thread as the siblings: Bayes four (two 16-byte stores), Dirichlet one (the scalar form of fused_head_kernel with
+// its v_pk_fma_f32 dot products), mean two (one 16-byte store).
+// Bayes decides through a table dec [C^E] (one byte per entry) built by the workgroup where C^E <= XV_MULTI_DEC_MAX, and sums
+// the E table rows per pixel above it.  The table pays for itself only while building it is cheaper than what it saves: an
+// entry costs what the per-pixel sum of one pixel costs (E row reads, E C adds, a C-way argmax), a workgroup has 1 024 pixels,
+// so 1 024 entries (four per thread) is where the table stops winning: two experts at any class count, three up to 10
+// classes, four up to 5.  Either way the sums and their order are bayes_fuse_kernel's.
+// LDS: tab [E][C][CM] (Dirichlet: transposed [E][CM k][CM c]), lognorm [E][CM], logprior [CM], dec.
+constexpr int XV_MULTI_MAXE = 4;
+constexpr int XV_MULTI_DEC_MAX = 1024;
+struct HeadPtrs {
+  const float* s[XV_MULTI_MAXE];
+  const float* b[XV_MULTI_MAXE];
+};
+
+// (selects on a wave-uniform index: a kernel argument array indexed at run time must not become a private copy)
+__device__ static __forceinline__ const float* head_ptr(const float* const (&p)[XV_MULTI_MAXE], int e) {
+  return e == 0 ? p[0] : (e == 1 ? p[1] : (e == 2 ? p[2] : p[3]));
+}
+
+constexpr int xv_multi_pixels(int mode) { return mode == 0 ? 4 : (mode == 1 ? 1 : 2); }
+
+static int multi_head_dec_entries(int num_classes, int num_experts) {
+  int64_t nd = 1;
+  for (int e = 0; e < num_experts; ++e) nd *= num_classes;
+  return nd <= XV_MULTI_DEC_MAX ? (int)nd : 0;
+}
+
+// waves per SIMD the register allocation is held to: at 12 classes what the two-expert siblings reach (Bayes and mean four,
+// Dirichlet eight with the class count folded and seven without); the wide Dirichlet forms are named too, because left alone
+// the compiler keeps table rows of the rolled expert loop in registers (16 classes, run-time count: 286 registers)
+constexpr int xv_multi_waves(int cm, int mode, bool full) {
+  if (mode != 1) return cm <= 12 ? 4 : 1;
+  return cm <= 8 ? 8 : (cm == 12 ? (full ? 8 : 7) : (cm <= 24 ? 4 : 3));
+}
+
+template <int CM, int MODE, bool FULL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_multi_waves(CM, MODE, FULL)))) void fused_head_multi_kernel(
+    HeadPtrs ptrs, int E, int N, int Hi, int Wi, int C_, int ndec, const float* __restrict__ tab_g,
+    const float* __restrict__ lognorm_g, const float* __restrict__ logprior_g, int64_t* __restrict__ fused) {
+  const int C = FULL ? CM : C_;
+  constexpr int P = xv_multi_pixels(MODE);
+  extern __shared__ __attribute__((aligned(16))) float tab[];
+  const int rows = MODE == 1 ? CM : C;  // table rows per expert
+  float* ln = tab + E * rows * CM;
+  float* lp = ln + E * CM;
+  uint8_t* dec = reinterpret_cast<uint8_t*>(lp + CM);  // [ndec]
+  if constexpr (MODE == 1) {
+    // transposed: tab[(e CM + k) CM + c] = alpha_e[c][k] - 1, two classes per v_pk_fma_f32 (below)
+    for (int i = threadIdx.x; i < E * CM * CM; i += 256) {
+      const int c = i % CM, k = (i / CM) % CM, e = i / (CM * CM);
+      tab[i] = (c < C && k < C) ? tab_g[(e * C + c) * C + k] : 0.f;
+    }
+    for (int i = threadIdx.x; i < E * CM; i += 256) {
+      const int k = i % CM, e = i / CM;
+      ln[i] = k < C ? lognorm_g[e * C + k] : 0.f;
+    }
+  }
+  if constexpr (MODE == 0) {
+    for (int i = threadIdx.x; i < E * C * CM; i += 256) {
+      const int k = i % CM, row = i / CM;
+      tab[i] = k < C ? tab_g[row * C + k] : 0.f;
+    }
+  }
+  if constexpr (MODE != 2) {
+    if (threadIdx.x < CM) lp[threadIdx.x] = threadIdx.x < C ? logprior_g[threadIdx.x] : 0.f;
+    __syncthreads();
+  }
+  if constexpr (MODE == 0) {
+    // dec[((l_0 C + l_1) C + ...) + l_{E-1}] = the label bayes_fuse_kernel gives these expert labels
+    if (ndec > 0) {
+      for (int i = threadIdx.x; i < ndec; i += 256) {
+        int l[XV_MULTI_MAXE], r = i;
+#pragma unroll
+        for (int e = XV_MULTI_MAXE - 1; e >= 0; --e) {
+          l[e] = 0;
+          if (e < E) {
+            l[e] = r % C;
+            r = r / C;
+          }
+        }
+        float best = 0.f;
+        int bi = 0;
+        for (int k = 0; k < C; ++k) {
+          float sc = tab[l[0] * CM + k];
+#pragma unroll
+          for (int e = 1; e < XV_MULTI_MAXE; ++e)
+            if (e < E) sc = sc + tab[(e * C + l[e]) * CM + k];
+          const float v = sc + lp[k];
+          if (k == 0 || v > best) {
+            best = v;
+            bi = k;
+          }
+        }
+        dec[i] = (uint8_t)bi;
+      }
+      __syncthreads();
+    }
+  }
+  const int Ho = Hi * 8, Wo = Wi * 8, Wq = Wo / P;
+  const int64_t nquads = (int64_t)N * Ho * Wq;
+  const int64_t quad = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (quad >= nquads) return;
+  const int ox0 = (int)(quad % Wq) * P;
+  const int oy = (int)((quad / Wq) % Ho);
+  const int n = (int)(quad / ((int64_t)Wq * Ho));
+  int iy1, ix1;
+  float wy1, wy0;
+  bilinear_taps<8>(oy, iy1, wy1, wy0);
+  {
+    float u1, u0;
+    bilinear_taps<8>(ox0, ix1, u1, u0);
+  }
+  // running state over the experts.  Bayes: the pixel's expert labels in one word, l_0 first: radix C where the table decides
+  // (the word IS the table index), 5 bits each where the rows are summed
+  constexpr int NT = MODE == 0 ? 1 : CM;
+  float total[P][NT];
+  int key[P];
+  const int radix = ndec > 0 ? C : 32;
+#pragma unroll
+  for (int p = 0; p < P; ++p) key[p] = 0;
+#pragma nounroll
+  for (int e = 0; e < E; ++e) {
+    const float* S = head_ptr(ptrs.s, e);
+    const float* bs = head_ptr(ptrs.b, e);
+    f32x4 ta[CM / 4], tb[CM / 4], tc[CM / 4], td[CM / 4];
+    head_load_taps<CM>(S, n, iy1, ix1, Hi, Wi, ta, tb, tc, td);
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      int ixp;
+      float wx1, wx0;
+      bilinear_taps<8>(ox0 + p, ixp, wx1, wx0);
+      if constexpr (MODE == 2) {
+        // one pixel after the other: left alone the scheduler interleaves them and each adds CM live registers (see
+        // fused_head_average_kernel); no instruction
+        if (p > 0) asm volatile("" : "+v"(wx1) : "v"(total[p - 1][CM - 1]));
+      }
+      float sc[CM];
+      head_eval_taps<CM>(ta, tb, tc, td, wy1, wy0, wx1, wx0, bs, C, sc);
+      const float m = head_max<CM>(sc, C);
+      if constexpr (MODE == 0) {
+        int l = head_label_fast<CM>(sc, m, C);
+        if (l < 0) l = head_softmax<CM>(sc, m, C);
+        key[p] = key[p] * radix + l;
+      } else if constexpr (MODE == 2) {
+        head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
+#pragma unroll
+        for (int k = 0; k < CM; ++k) total[p][k] = e == 0 ? sc[k] : total[p][k] + sc[k];
+      } else {
+        head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < CM; ++k) {
+          sc[k] = k < C ? sc[k] : 0.f;
+          sum += sc[k];
+        }
+        {
+          const float rs = xv_fast_rcp(sum);
+#pragma unroll
+          for (int k = 0; k < CM; ++k) sc[k] = k < C ? xv_fast_log(1e-20f + sc[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
+        }
+        // the fmaf chain over k of dirichlet_fuse_kernel per class, two classes per v_pk_fma_f32 on the transposed table
+        // (padded classes / terms are exact zeros: fma(0, 0, d) = d), as fused_head_kernel
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        f32x2 dot2[CM / 2];
+#pragma unroll
+        for (int cp = 0; cp < CM / 2; ++cp) dot2[cp] = f32x2{0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < CM; ++k) {
+          const f32x2* rowk = reinterpret_cast<const f32x2*>(tab + (e * CM + k) * CM);
+          const f32x2 lk = f32x2{sc[k], sc[k]};
+#pragma unroll
+          for (int cp = 0; cp < CM / 2; ++cp) dot2[cp] = __builtin_elementwise_fma(rowk[cp], lk, dot2[cp]);
+        }
+#pragma unroll
+        for (int c = 0; c < CM; ++c) {
+          const float L = dot2[c >> 1][c & 1] - ln[e * CM + c];
+          total[p][c] = c < C ? (e == 0 ? L : total[p][c] + L) : 0.f;
+        }
+      }
+    }
+  }
+  int64_t out[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    float best = 0.f;
+    int bi = 0;
+    if constexpr (MODE == 0) {
+      if (ndec > 0) {
+        bi = dec[key[p]];
+      } else {
+        // bayes_fuse_kernel: the E rows of the pixel's labels summed in ascending expert order
+        float sc[CM];
+#pragma nounroll
+        for (int e = 0; e < E; ++e) {
+          const int l = (key[p] >> (5 * (E - 1 - e))) & 31;
+          const f32x4* row = reinterpret_cast<const f32x4*>(tab + (e * C + l) * CM);
+#pragma unroll
+          for (int k4 = 0; k4 < CM / 4; ++k4) {
+            const f32x4 r = row[k4];
+            sc[4 * k4] = e == 0 ? r.x : sc[4 * k4] + r.x;
+            sc[4 * k4 + 1] = e == 0 ? r.y : sc[4 * k4 + 1] + r.y;
+            sc[4 * k4 + 2] = e == 0 ? r.z : sc[4 * k4 + 2] + r.z;
+            sc[4 * k4 + 3] = e == 0 ? r.w : sc[4 * k4 + 3] + r.w;
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < CM; ++k) {
+          const float v = sc[k] + lp[k];
+          if (k < C && (k == 0 || v > best)) {
+            best = v;
+            bi = k;
+          }
+        }
+      }
+    } else {
+      const float fe = (float)E;
+#pragma unroll
+      for (int k = 0; k < CM; ++k) {
+        const float v = MODE == 1 ? total[p][k] + lp[k] : total[p][k] / fe;
+        if (k < C && (k == 0 || v > best)) {
+          best = v;
+          bi = k;
+        }
+      }
+    }
+    out[p] = bi;
+  }
+  int64_t* dst = fused + quad * P;
+  if constexpr (P % 2 == 0) {
+    typedef __attribute__((ext_vector_type(2))) long long i64x2;
+#pragma unroll
+    for (int p = 0; p < P; p += 2) *reinterpret_cast<i64x2*>(dst + p) = i64x2{out[p], out[p + 1]};
+  } else {
+#pragma unroll
+    for (int p = 0; p < P; ++p) dst[p] = out[p];
+  }
+}
+
 // ---- softmax + argmax on dense fp32 scores (basic_fusion_model.py:21-22) -------------------------
 template <int CMAX>
 __global__ __launch_bounds__(256) void softmax_argmax_kernel(const float* __restrict__ score, int64_t npix, int C,
@@ -1494,6 +1748,60 @@ extern "C" int xv_fused_head_average_count_fwd(const float* Sa, const float* Sb,
   return xv_launch_status();
 }
 #undef XV_FA_LAUNCH
+
+// Fused head of a fusion model with two to four experts (see fused_head_multi_kernel): S[e] from xv_score_lowres of expert e's
+// `fused` map.  mode 0 = Bayes (tab = loglik [E][C][C]), 1 = Dirichlet (tab = am1 [E][C][C], lognorm [E][C]), 2 = mean (no
+// tables).  Everything is checked before anything is launched.
+extern "C" int xv_fused_head_multi_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                       int num_classes, int mode, const float* tab, const float* lognorm,
+                                       const float* logprior, int64_t* fused_label, void* stream) {
+  XV_CHECK_ARG(S && bias && fused_label && ((uintptr_t)fused_label & 15) == 0);
+  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
+  XV_CHECK_ARG(mode >= 0 && mode <= 2 && n > 0 && hi > 0 && wi > 0);
+  XV_CHECK_ARG(mode == 2 || (tab && logprior && ((uintptr_t)tab & 3) == 0 && ((uintptr_t)logprior & 3) == 0));
+  XV_CHECK_ARG(mode != 1 || (lognorm && ((uintptr_t)lognorm & 3) == 0));
+  HeadPtrs ptrs;
+  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
+    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
+    XV_CHECK_ARG(S[src] && bias[src] && ((uintptr_t)S[src] & 15) == 0 && ((uintptr_t)bias[src] & 3) == 0);  // 16-byte tap loads
+    ptrs.s[e] = S[src];
+    ptrs.b[e] = bias[src];
+  }
+  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  const int64_t nquads = (int64_t)n * hi * wi * 64 / xv_multi_pixels(mode);  // (8 wi is a multiple of every pixel group)
+  XV_CHECK_SHAPE((nquads + 255) / 256 <= 0x7fffffff);
+  const unsigned grid = (unsigned)((nquads + 255) / 256);
+  const int ndec = mode == 0 ? multi_head_dec_entries(num_classes, num_experts) : 0;
+  hipStream_t s = (hipStream_t)stream;
+#define XV_FM_MODE(CMV, MODE, FULL)                                                                                        \
+  hipLaunchKernelGGL((fused_head_multi_kernel<CMV, MODE, FULL>), dim3(grid), dim3(256), lds, s, ptrs, num_experts, n, hi, wi, \
+                     num_classes, ndec, tab, lognorm, logprior, fused_label)
+#define XV_FM(CMV)                                                                                                      \
+  {                                                                                                                     \
+    const size_t lds = mode == 2 ? 0                                                                                    \
+                                 : (size_t)(num_experts * (mode == 1 ? CMV : num_classes) * CMV + (num_experts + 1) * CMV) * 4 + \
+                                       (size_t)(ndec + 15) / 16 * 16;                                                   \
+    if (num_classes == CMV) {                                                                                           \
+      if (mode == 0)                                                                                                    \
+        XV_FM_MODE(CMV, 0, true);                                                                                       \
+      else if (mode == 1)                                                                                               \
+        XV_FM_MODE(CMV, 1, true);                                                                                       \
+      else                                                                                                              \
+        XV_FM_MODE(CMV, 2, true);                                                                                       \
+    } else {                                                                                                            \
+      if (mode == 0)                                                                                                    \
+        XV_FM_MODE(CMV, 0, false);                                                                                      \
+      else if (mode == 1)                                                                                               \
+        XV_FM_MODE(CMV, 1, false);                                                                                      \
+      else                                                                                                              \
+        XV_FM_MODE(CMV, 2, false);                                                                                      \
+    }                                                                                                                   \
+  }
+  XV_CM_SWITCH(num_classes, XV_FM)
+#undef XV_FM
+#undef XV_FM_MODE
+  return xv_launch_status();
+}
 
 // Variance head of the MC-dropout fusion model (see variance_head_kernel): Sa / Sb from xv_score_lowres of each expert's
 // (T+1) n-image `fused` map, [(T+1) n][hi+2][wi+2][CP] each.

@@ -112,6 +112,10 @@ class DirichletFusion(FusionModel):
     def _fused_head(self):
         return lambda *scores: ops.fused_head(*scores, self.config['num_classes'], self.am1, self.logprior, lognorm=self.lognorm)
 
+    def _multi_head(self):
+        return lambda *scores: ops.fused_head_multi(*scores, self.config['num_classes'], 'dirichlet', tab=self.am1,
+                                                    lognorm=self.lognorm, logprior=self.logprior)
+
     def _fusion(self, expert_outputs, output_attr=None):
         probs = [expert_outputs[m]['prob'] for m in self.modalities]
         self.probs = dict(zip(self.modalities, probs))

@@ -733,6 +733,43 @@ def fused_head_average(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, out=None)
     return out
 
 
+FUSED_HEAD_MODES = {'bayes': 0, 'dirichlet': 1, 'mean': 2}
+
+
+def fused_head_multi(scores, biases, n, hi, wi, num_classes, mode, tab=None, lognorm=None, logprior=None, out=None):
+    """Two to four experts' low-resolution scores (lists of E tensors, scores float32 [n][hi+2][wi+2][CP], biases float32 [C])
+    -> the fused label map (int64 [n, 8hi, 8wi]) in one launch.  mode 0 / 'bayes': tab = log-likelihood tables [E,C,C] and
+    logprior [C], the labels of bayes_fuse on the experts' label maps; 1 / 'dirichlet': tab = alpha - 1 [E,C,C], lognorm [E,C],
+    logprior, the labels of dirichlet_fuse on their probability maps; 2 / 'mean': no tables, the labels of average_fuse --
+    bit for bit, and none of those maps is written."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    scores, biases = list(scores), list(biases)
+    if len(scores) != len(biases):
+        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
+    cp = (int(num_classes) + 3) // 4 * 4
+    for i, (S, b) in enumerate(zip(scores, biases)):
+        _need(S, torch.float32, 'scores[%d]' % i)
+        _need(b, torch.float32, 'biases[%d]' % i)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+        if b.numel() != int(num_classes):
+            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), int(num_classes)))
+    e, c = len(scores), int(num_classes)
+    for name, t, shape in (('tab', tab, (e, c, c)), ('lognorm', lognorm, (e, c)), ('logprior', logprior, (c,))):
+        if t is not None:
+            _need(t, torch.float32, name)
+            if tuple(t.shape) != shape:
+                raise ValueError('%s of shape %s, expected %s' % (name, tuple(t.shape), shape))
+    if out is None:
+        out = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.int64, device=scores[0].device)
+    elif out.dtype != torch.int64 or out.numel() != n * hi * wi * 64:
+        raise ValueError('out must be int64 of %d elements' % (n * hi * wi * 64))
+    rc = _lib.lib().xv_fused_head_multi_fwd(_ptr_array(scores), _ptr_array(biases), e, int(n), int(hi), int(wi), c, int(mode),
+                                           _ptr(tab), _ptr(lognorm), _ptr(logprior), _ptr(out), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_fwd')
+    return out
+
+
 def fused_head_average_count(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, cm=None, max_workgroups=0):
     """Both experts' low-resolution scores, average-fused and counted against labels (int32 [n, 8hi, 8wi]): accumulates into cm
     (int64 [C,C], rows = ground truth; made here when None) as confusion_matrix would count fused_head_average's labels, and
