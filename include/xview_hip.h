@@ -545,6 +545,32 @@ int xv_fused_head_multi_fwd(const float* const* S, const float* const* bias, int
                             int num_classes, int mode, const float* tab, const float* lognorm, const float* logprior,
                             int64_t* fused_label, void* stream);
 
+/* Counting form of xv_fused_head_multi_fwd: S, bias, num_experts (2..4), n, hi, wi, num_classes (2..32) and mode as that
+ * function takes them; num_points parameter sets G:
+ *   mode 0, Bayes:     tab [E][C][C] shared by all points (the log-likelihoods do not depend on the prior), logprior [G][C];
+ *   mode 1, Dirichlet: tab [G][E][C][C] (alpha - 1), lognorm [G][E][C], logprior [G][C];
+ *   mode 2, mean:      no tables (may be NULL), num_points must be 1.
+ * Every output pixel is fused under all G sets -- fused_g is the label xv_fused_head_multi_fwd writes with point g's tables,
+ * bit for bit -- and counted against labels int32 [n][8hi][8wi] as xv_confusion_matrix would: cm int64
+ * [num_groups][G][C][C] (rows = ground truth), cm[group[i]][g][label][fused_g] += 1 over the pixels with 0 <= label < C.
+ * expert_cm (may be NULL) int64 [num_groups][E][C][C]: expert_cm[group[i]][e][label][l_e] += 1 with l_e the label
+ * xv_decoder_head_fwd gives expert e.  Both are accumulated, not cleared; no label map is written.  group (may be NULL, then
+ * num_groups must be 1) int32 [n] in DEVICE memory as xv_fused_head_joint_hist_grouped_fwd takes it: a workgroup handles one
+ * image at a time and flushes once per image, an id outside [0, num_groups) counts nothing, group g's slice is the ungrouped
+ * call on g's images alone.  max_workgroups bounds the grid (0: the kernel's own bound).  XV_EINVAL, with nothing launched and
+ * the outputs untouched, for num_experts outside 2..4, num_classes outside 2..32, an unknown mode, num_points < 1, above
+ * xv_fused_head_multi_count_capacity or not 1 in mode 2, non-positive sizes, max_workgroups < 0, num_groups < 1 (or not 1
+ * without group), or a null or misaligned pointer the mode needs.                                                          */
+int xv_fused_head_multi_count_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                  int num_classes, int mode, int num_points, const float* tab, const float* lognorm,
+                                  const float* logprior, const int32_t* labels, const int32_t* group, int num_groups,
+                                  int64_t* cm, int64_t* expert_cm, int max_workgroups, void* stream);
+
+/* Most parameter sets one xv_fused_head_multi_count_fwd launch takes (tables and counters share 40 KB of one workgroup's LDS
+ * beside the expert counters, which always keep their room): 12 for 12 classes, four experts, Dirichlet; at least 1 up to 32
+ * classes and four experts in every mode, within the same 40 KB; 1 in mode 2; 0 outside the supported ranges.  No GPU call. */
+int xv_fused_head_multi_count_capacity(int num_classes, int num_experts, int mode);
+
 /* Counting form of the fused average head: cm int64 [C][C] (rows = ground truth), cm[label][fused] += 1 over the pixels with
  * 0 <= label < C (labels int32 [n][8hi][8wi], 16-byte aligned) as xv_confusion_matrix would count xv_fused_head_average_fwd's
  * labels: accumulated, not cleared; no label map is written.  max_workgroups bounds the grid (0: the kernel's own bound).

@@ -289,7 +289,8 @@ def output_key(output_attr):
 # The reference builds and evaluates one model per grid point.  The parameters of the fusion itself (class prior, sigma, the
 # regularisation of the Dirichlet fit) never reach the experts, so a fusion model scores all of them on one pass: the experts
 # run once per batch and only the fusion and the counting are repeated -- inside one kernel where the fused head serves the
-# model (score_grid_fused), through the fusion kernels on the experts' materialised outputs otherwise (score_grid_generic).
+# model (score_grid_fused; score_grid_fused_multi for three or four experts), through the fusion kernels on the experts'
+# materialised outputs otherwise (score_grid_generic).
 # Both count the same integers.  The pass runs eagerly (no hipGraph capture: it is not the step predict() replays).
 
 def parameter_combinations(search_parameters, net_config):
@@ -321,6 +322,19 @@ def score_grid_fused(model, data, counts, count_batch, max_iterations=None):
     labels, counts) accumulates into the device tensor `counts`."""
     for batch, labels in _labelled_batches(model, data, max_iterations):
         count_batch(*run_lowres_scores(model, batch), labels, counts)
+    return counts
+
+
+def score_grid_fused_multi(model, data, mode, num_points, max_iterations=None, **tables):
+    """The fused route of three or four experts (multi_head_applicable): per batch every trunk once up to its low-resolution
+    scores (run_lowres_scores_multi), then ONE ops.fused_head_multi_count launch fuses every pixel under all `num_points`
+    parameter sets (`tables`: tab, lognorm, logprior as that op takes them for `mode`) and counts it.  Returns the int64
+    [G, C, C] counts."""
+    from . import ops
+    C = model.config['num_classes']
+    counts = torch.zeros((num_points, C, C), dtype=torch.int64, device=model.device)
+    for batch, labels in _labelled_batches(model, data, max_iterations):
+        ops.fused_head_multi_count(*run_lowres_scores_multi(model, batch), C, mode, labels, cm=counts, **tables)
     return counts
 
 

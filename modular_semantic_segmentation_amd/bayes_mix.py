@@ -7,7 +7,8 @@ import torch
 from . import ops
 from .base_model import grouped_batches
 from .basic_fusion_model import (FusionModel, device_tables, fused_head_applicable, grid_point_configs, grid_results,
-                                 reduce_over_ranks, run_lowres_scores, score_grid_fused, score_grid_generic)
+                                 multi_head_applicable, reduce_over_ranks, run_lowres_scores, score_grid_fused,
+                                 score_grid_fused_multi, score_grid_generic)
 
 UNIFORM_PRIOR = 1.0 / 14     # the reference hard-codes 1/14 regardless of num_classes (bayes_mix.py:42,95)
 
@@ -168,6 +169,13 @@ class BayesFusion(FusionModel):
             counts = [confusion_from_joint_hist(hist, fused_decision_table(*bayes_tables(mats, c['class_prior'])))
                       for c in configs]
             return grid_results(configs, counts)
+        if not lut and multi_head_applicable(self):
+            # three or four experts: the log-likelihoods come from the matrices alone, a prior only changes logprior
+            logprior = torch.stack([device_tables(self.device, bayes_tables(mats, c['class_prior'])[1])[0] for c in configs])
+            counts = score_grid_fused_multi(self, data, 'bayes', len(configs), max_iterations, tab=self.loglik,
+                                            logprior=logprior.contiguous())
+            reduce_over_ranks(self, counts)
+            return grid_results(configs, counts.cpu().numpy())
         if lut and len(self.modalities) == 2:
             luts = device_tables(self.device, *[bayes_decision_matrix(mats, c['class_prior']).astype(np.int64) for c in configs])
 

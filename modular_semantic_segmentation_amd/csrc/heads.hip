@@ -1162,17 +1162,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 
 // so 1 024 entries (four per thread) is where the table stops winning: two experts at any class count, three up to 10
 // classes, four up to 5.  Either way the sums and their order are bayes_fuse_kernel's.
 // LDS: tab [E][C][CM] (Dirichlet: transposed [E][CM k][CM c]), lognorm [E][CM], logprior [CM], dec.
-constexpr int XV_MULTI_MAXE = 4;
+// (XV_MULTI_MAXE, HeadPtrs and head_ptr: xv_heads.h, shared with the counting form in multi_count.hip)
 constexpr int XV_MULTI_DEC_MAX = 1024;
-struct HeadPtrs {
-  const float* s[XV_MULTI_MAXE];
-  const float* b[XV_MULTI_MAXE];
-};
-
-// (selects on a wave-uniform index: a kernel argument array indexed at run time must not become a private copy)
-__device__ static __forceinline__ const float* head_ptr(const float* const (&p)[XV_MULTI_MAXE], int e) {
-  return e == 0 ? p[0] : (e == 1 ? p[1] : (e == 2 ? p[2] : p[3]));
-}
 
 constexpr int xv_multi_pixels(int mode) { return mode == 0 ? 4 : (mode == 1 ? 1 : 2); }
 

@@ -132,3 +132,16 @@ __device__ static __forceinline__ void xv_wave_count(uint32_t* cells, int key) {
 
 // output pixels per thread of the joint-histogram heads: four up to 12 classes, two above (fused_head_joint_hist_kernel)
 constexpr int xv_joint_hist_pixels(int cm) { return cm <= 12 ? 4 : 2; }
+
+// Score and bias pointers of the two to four experts of fused_head_multi_kernel (heads.hip) and its counting form
+// (multi_count.hip), as kernel arguments: no pointer table in device memory.
+constexpr int XV_MULTI_MAXE = 4;
+struct HeadPtrs {
+  const float* s[XV_MULTI_MAXE];
+  const float* b[XV_MULTI_MAXE];
+};
+
+// (selects on a wave-uniform index: a kernel argument array indexed at run time must not become a private copy)
+__device__ static __forceinline__ const float* head_ptr(const float* const (&p)[XV_MULTI_MAXE], int e) {
+  return e == 0 ? p[0] : (e == 1 ? p[1] : (e == 2 ? p[2] : p[3]));
+}

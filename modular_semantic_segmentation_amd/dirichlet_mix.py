@@ -7,8 +7,9 @@ from scipy.special import gammaln
 
 from . import ops
 from .basic_fusion_model import (FusionModel, calibrate_experts, device_tables, engine_options, expert_factory,  # noqa: F401
-                                 fused_head_applicable, grid_point_configs, grid_results, measure_experts, reduce_over_ranks,
-                                 run_experts, score_grid_fused, score_grid_generic, test_pipeline)
+                                 fused_head_applicable, grid_point_configs, grid_results, measure_experts,
+                                 multi_head_applicable, reduce_over_ranks, run_experts, score_grid_fused,
+                                 score_grid_fused_multi, score_grid_generic, test_pipeline)
 from .dirichlet_fit import find_dirichlet_priors
 
 UNIFORM_PRIOR = 1.0 / 14     # dirichlet_mix.py:116
@@ -191,6 +192,10 @@ class DirichletFusion(FusionModel):
             def count_batch(Sa, Sb, ba, bb, n, hi, wi, labels, cm):
                 ops.fused_head_grid_score(Sa, Sb, ba, bb, n, hi, wi, C, am1, lognorm, logprior, labels, cm=cm)
             score_grid_fused(self, data, counts, count_batch, max_iterations)
+        elif multi_head_applicable(self):
+            am1, lognorm, logprior = (torch.stack([point[i] for point in tables]).contiguous() for i in range(3))
+            counts = score_grid_fused_multi(self, data, 'dirichlet', len(configs), max_iterations, tab=am1, lognorm=lognorm,
+                                            logprior=logprior)
         else:
             def fuse_point(outs, g):
                 return ops.dirichlet_fuse([outs[m]['prob'] for m in self.modalities], *tables[g])[0]

@@ -17,7 +17,8 @@ import torch
 from . import ops
 from .base_model import grouped_batches, grouped_results, groups_seen, image_groups, score_measures
 from .basic_fusion_model import (FusionModel, _labelled_batches, device_tables, fused_head_applicable, measure_experts,
-                                 reduce_over_ranks, run_experts, run_lowres_scores)
+                                 multi_head_applicable, reduce_over_ranks, run_experts, run_lowres_scores,
+                                 run_lowres_scores_multi)
 from .bayes_mix import BayesFusion, bayes_tables, confusion_from_joint_hist, fused_decision_table
 from .dirichlet_mix import dirichlet_tables, fit_dirichlet_params
 
@@ -91,7 +92,23 @@ class FusionComparison(FusionModel):
 
     # ---- score everything on one pass -------------------------------------------------------------------
     def one_pass_heads_applicable(self):
+        """Two experts: the joint-histogram, grid-scoring and average counting heads (up to the joint histogram's class count);
+        three or four: ops.fused_head_multi_count, which has no such limit."""
+        return multi_head_applicable(self) or self._two_expert_heads_applicable()
+
+    def _two_expert_heads_applicable(self):
         return fused_head_applicable(self) and self.config['num_classes'] <= BayesFusion.JOINT_HIST_MAX_CLASSES
+
+    def _count_multi(self, head_args, labels, fused, experts, **groups):
+        """Three or four experts, one batch: three counting launches on the same low-resolution scores -- Bayes (which also
+        counts every expert's own matrix), Dirichlet with one point, mean -- into fused [3] and experts."""
+        C = self.config['num_classes']
+        am1, lognorm, logprior = self.dirichlet
+        ops.fused_head_multi_count(*head_args, C, 'bayes', labels, tab=self.bayes[2], logprior=self.bayes[3][None].contiguous(),
+                                   cm=fused[0], expert_cm=experts, **groups)
+        ops.fused_head_multi_count(*head_args, C, 'dirichlet', labels, tab=am1[None].contiguous(),
+                                   lognorm=lognorm[None].contiguous(), logprior=logprior[None].contiguous(), cm=fused[1], **groups)
+        ops.fused_head_multi_count(*head_args, C, 'mean', labels, cm=fused[2], **groups)
 
     def _require_measurements(self):
         if self.bayes is None or self.dirichlet is None:
@@ -125,7 +142,14 @@ class FusionComparison(FusionModel):
         self._require_measurements()
         C = self.config['num_classes']
         am1, lognorm, logprior = self.dirichlet
-        if self.one_pass_heads_applicable():
+        if multi_head_applicable(self):
+            fused = torch.zeros((3, 1, C, C), dtype=torch.int64, device=self.device)       # Bayes, Dirichlet, average
+            experts = torch.zeros((len(self.modalities), C, C), dtype=torch.int64, device=self.device)
+            for batch, labels in _labelled_batches(self, test_set, max_iterations):
+                self._count_multi(run_lowres_scores_multi(self, batch), labels, fused, experts)
+            reduce_over_ranks(self, fused, experts)
+            matrices = list(experts.cpu().numpy()) + list(fused[:, 0].cpu().numpy())
+        elif self._two_expert_heads_applicable():
             hist = torch.zeros((C, C, C), dtype=torch.int64, device=self.device)
             counts = torch.zeros((2, C, C), dtype=torch.int64, device=self.device)         # Dirichlet, average
             tabs = (am1[None].contiguous(), lognorm[None].contiguous(), logprior[None].contiguous())
@@ -152,7 +176,8 @@ class FusionComparison(FusionModel):
         """score_all per group of images on ONE pass of the experts: {key: what score_all returns for the images of that key}.
         groups as BaseModel.score_groups takes them: one hashable key per image in data order, or 'image'.  On the one-pass
         heads the grouped joint histogram gives both experts and Bayes; the Dirichlet and the average label maps (fused heads)
-        are counted by the grouped confusion kernel."""
+        are counted by the grouped confusion kernel.  With three or four experts the
+        counting head takes the group ids itself: the three launches of score_all, a matrix per group each."""
         self._require_measurements()
         C = self.config['num_classes']
         am1, lognorm, logprior = self.dirichlet
@@ -161,7 +186,15 @@ class FusionComparison(FusionModel):
         G, scored = len(keys), [0]
         if not keys:
             return {}
-        if self.one_pass_heads_applicable():
+        if multi_head_applicable(self):
+            fused = torch.zeros((3, G, 1, C, C), dtype=torch.int64, device=self.device)    # Bayes, Dirichlet, average
+            experts = torch.zeros((G, len(self.modalities), C, C), dtype=torch.int64, device=self.device)
+            for batch, labels, batch_ids in grouped_batches(self, test_set, ids, G, max_iterations, scored):
+                self._count_multi(run_lowres_scores_multi(self, batch), labels, fused, experts, groups=batch_ids, num_groups=G)
+            reduce_over_ranks(self, fused, experts)
+            fused, experts = fused.cpu().numpy(), experts.cpu().numpy()
+            matrices = [list(experts[g]) + [fused[i][g][0] for i in range(3)] for g in range(G)]
+        elif self._two_expert_heads_applicable():
             hist = torch.zeros((G, C, C, C), dtype=torch.int64, device=self.device)
             counts = torch.zeros((2, G, C, C), dtype=torch.int64, device=self.device)      # Dirichlet, average
             for batch, labels, batch_ids in grouped_batches(self, test_set, ids, G, max_iterations, scored):

@@ -770,6 +770,86 @@ def fused_head_multi(scores, biases, n, hi, wi, num_classes, mode, tab=None, log
     return out
 
 
+def fused_head_multi_count_capacity(num_classes, num_experts, mode):
+    """Most parameter sets one xv_fused_head_multi_count_fwd launch takes (0: nothing of that kind is served)."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    return int(_lib.lib().xv_fused_head_multi_count_capacity(int(num_classes), int(num_experts), int(mode)))
+
+
+def fused_head_multi_count(scores, biases, n, hi, wi, num_classes, mode, labels, tab=None, lognorm=None, logprior=None,
+                           groups=None, num_groups=1, cm=None, expert_cm=None, max_workgroups=0):
+    """Counting form of fused_head_multi: two to four experts' low-resolution scores, fused under G parameter sets at once and
+    counted against labels (int32 [n, 8hi, 8wi]) without a label map.  mode 0 / 'bayes': tab [E,C,C] shared by all sets,
+    logprior [G,C]; 1 / 'dirichlet': tab [G,E,C,C], lognorm [G,E,C], logprior [G,C]; 2 / 'mean': no tables, G = 1.
+    Accumulates into cm (int64 [num_groups,G,C,C], or [G,C,C] without groups; rows = ground truth; made here when None) and
+    returns it.  expert_cm (int64 [num_groups,E,C,C] / [E,C,C]) also takes every expert's own confusion matrix.  `groups`
+    as fused_head_joint_hist_grouped takes it.  More sets than one launch holds (fused_head_multi_count_capacity) go in
+    several launches on the same scores; expert_cm is counted by the first one only."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError('unknown fused head mode %r' % (mode,))
+    scores, biases = list(scores), list(biases)
+    if len(scores) != len(biases):
+        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
+    E, C, NG = len(scores), int(num_classes), int(num_groups)
+    cp = (C + 3) // 4 * 4
+    for i, (S, b) in enumerate(zip(scores, biases)):
+        _need(S, torch.float32, 'scores[%d]' % i)
+        _need(b, torch.float32, 'biases[%d]' % i)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+        if b.numel() != C:
+            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
+    _need(labels, torch.int32, 'labels')
+    if labels.numel() != n * hi * wi * 64:
+        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+    if mode == 2:
+        if tab is not None or lognorm is not None or logprior is not None:
+            raise ValueError('the mean takes no tables')
+        G = 1
+    else:
+        if tab is None or logprior is None or (mode == 1 and lognorm is None):
+            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
+        G = int(logprior.shape[0]) if logprior.dim() == 2 else 0
+        shapes = ((('tab', tab, (E, C, C)),) if mode == 0 else (('tab', tab, (G, E, C, C)), ('lognorm', lognorm, (G, E, C))))
+        for name, t, shape in shapes + (('logprior', logprior, (G, C)),):
+            _need(t, torch.float32, name)
+            if G < 1 or tuple(t.shape) != shape:
+                raise ValueError('%s of shape %s, expected %s with G >= 1' % (name, tuple(t.shape), shape))
+    ids = None
+    if groups is not None:
+        ids = _group_ids(groups, n, NG, scores[0].device)
+    elif NG != 1:
+        raise ValueError('num_groups = %d without groups' % NG)
+    lead = (NG,) if groups is not None else ()
+    if cm is None:
+        cm = torch.zeros(lead + (G, C, C), dtype=torch.int64, device=scores[0].device)
+    _need(cm, torch.int64, 'cm')
+    if tuple(cm.shape) != lead + (G, C, C):
+        raise ValueError('cm of shape %s, expected %s' % (tuple(cm.shape), lead + (G, C, C)))
+    if expert_cm is not None:
+        _need(expert_cm, torch.int64, 'expert_cm')
+        if tuple(expert_cm.shape) != lead + (E, C, C):
+            raise ValueError('expert_cm of shape %s, expected %s' % (tuple(expert_cm.shape), lead + (E, C, C)))
+    cap = fused_head_multi_count_capacity(C, E, mode)
+    if cap < 1:
+        raise ValueError('no counting head for %d experts, %d classes, mode %d' % (E, C, mode))
+    S_arr, b_arr = _ptr_array(scores), _ptr_array(biases)
+    for g0 in range(0, G, cap):
+        g1 = min(G, g0 + cap)
+        # a launch writes cm [num_groups][g1 - g0][C][C] densely: a slice of the points of a grouped cm is counted apart
+        part = cm if (g0, g1) == (0, G) else (cm[g0:g1] if groups is None else
+                                             torch.zeros((NG, g1 - g0, C, C), dtype=torch.int64, device=cm.device))
+        rc = _lib.lib().xv_fused_head_multi_count_fwd(
+            S_arr, b_arr, E, int(n), int(hi), int(wi), C, int(mode), g1 - g0, _ptr(tab if mode != 1 else tab[g0:g1]),
+            _ptr(None if mode != 1 else lognorm[g0:g1]), _ptr(None if mode == 2 else logprior[g0:g1]), _ptr(labels), _ptr(ids),
+            NG, _ptr(part), _ptr(expert_cm if g0 == 0 else None), int(max_workgroups), _stream())
+        _lib.check(rc, 'xv_fused_head_multi_count_fwd')
+        if part is not cm and groups is not None:
+            cm[:, g0:g1] += part
+    return cm
+
+
 def fused_head_average_count(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, cm=None, max_workgroups=0):
     """Both experts' low-resolution scores, average-fused and counted against labels (int32 [n, 8hi, 8wi]): accumulates into cm
     (int64 [C,C], rows = ground truth; made here when None) as confusion_matrix would count fused_head_average's labels, and
