@@ -4,13 +4,7 @@
 #include <stdlib.h>
 
 #include "xv_common.h"
-
-// Floating-point contraction by the SOURCE only (a * b + c inside one expression), never across statements: the fused
-// two-expert head and the unfused path (decoder head -> probability maps -> fusion kernel) must produce the same bits, and
-// under the default -ffp-contract=fast the optimizer fuses a product into a later sum wherever the two happen to meet --
-// round 4: specialising the fused head on the class count removed a select between `p = e * rsum` and `sum += p`, the
-// compiler made it an fma there and not in the kernel that reads p back from memory, and one pixel in a million flipped.
-#pragma clang fp contract(on)
+#include "xv_fuse.h"  // the fusion of a pixel, shared with the fused heads (sets `fp contract(on)` for what follows)
 
 namespace {
 
@@ -48,10 +42,7 @@ __global__ __launch_bounds__(256) void bayes_fuse_kernel(LabelPtrs labels, int E
                                                         int64_t* __restrict__ fused, float* __restrict__ score_out) {
   extern __shared__ __attribute__((aligned(16))) float tab[];  // [E][C][CMAX] then [CMAX]
   float* lp = tab + E * C * CMAX;
-  for (int i = threadIdx.x; i < E * C * CMAX; i += 256) {
-    const int k = i % CMAX, row = i / CMAX;
-    tab[i] = k < C ? loglik[row * C + k] : 0.f;
-  }
+  fuse_stage_rows<CMAX>(tab, loglik, E * C, C);
   if (threadIdx.x < CMAX) lp[threadIdx.x] = threadIdx.x < C ? logprior[threadIdx.x] : 0.f;
   __syncthreads();
   for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * 256) {
@@ -153,14 +144,8 @@ __global__ __launch_bounds__(256) void dirichlet_fuse_kernel(ProbPtrs probs, int
   extern __shared__ __attribute__((aligned(16))) float tab[];  // am1 [E][C][CMAX], lognorm [E][CMAX], logprior [CMAX]
   float* ln = tab + E * C * CMAX;
   float* lp = ln + E * CMAX;
-  for (int i = threadIdx.x; i < E * C * CMAX; i += 256) {
-    const int k = i % CMAX, row = i / CMAX;
-    tab[i] = k < C ? am1[row * C + k] : 0.f;
-  }
-  for (int i = threadIdx.x; i < E * CMAX; i += 256) {
-    const int k = i % CMAX, e = i / CMAX;
-    ln[i] = k < C ? lognorm[e * C + k] : 0.f;
-  }
+  fuse_stage_rows<CMAX>(tab, am1, E * C, C);
+  fuse_stage_rows<CMAX>(ln, lognorm, E, C);
   if (threadIdx.x < CMAX) lp[threadIdx.x] = threadIdx.x < C ? logprior[threadIdx.x] : 0.f;
   __syncthreads();
   for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * 256) {
@@ -181,12 +166,7 @@ __global__ __launch_bounds__(256) void dirichlet_fuse_kernel(ProbPtrs probs, int
       } else {
         load_row<CMAX>(probs.p[e] + pix * C, C, vec, lx);
       }
-      float sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < CMAX; ++k) sum += lx[k];
-      const float rs = xv_fast_rcp(sum);  // (the same helper forms as the fused head: xv_common.h)
-#pragma unroll
-      for (int k = 0; k < CMAX; ++k) lx[k] = k < C ? xv_fast_log(1e-20f + lx[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
+      fuse_renorm_log<CMAX, false>(lx, C);  // (load_row pads with zeros: no mask)
       if (EXACT) {
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) {
@@ -244,16 +224,11 @@ __global__ __launch_bounds__(256) void dirichlet_fuse_pk_kernel(const float* __r
                                                                const float* __restrict__ am1, const float* __restrict__ lognorm,
                                                                const float* __restrict__ logprior, int64_t npix,
                                                                int64_t* __restrict__ fused, float* __restrict__ score_out) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int H2 = CM / 2;
   extern __shared__ __attribute__((aligned(16))) float tab[];
   float* ln = tab + 2 * CM * CM;
   float* lp = ln + 2 * CM;
-  for (int i = threadIdx.x; i < 2 * CM * CM; i += 256) {
-    const int c = i % CM, k = (i / CM) % CM, e = i / (CM * CM);
-    tab[i] = am1[(e * CM + c) * CM + k];
-  }
-  for (int i = threadIdx.x; i < 2 * CM; i += 256) ln[i] = lognorm[i];
+  fuse_stage_dirichlet<CM>(tab, ln, am1, lognorm, 2, CM);
   if (threadIdx.x < CM) lp[threadIdx.x] = logprior[threadIdx.x];
   __syncthreads();
   const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -333,17 +308,7 @@ __global__ __launch_bounds__(256) void average_fuse_kernel(ProbPtrs probs, int E
 #pragma unroll
       for (int k = 0; k < CMAX; ++k) s[k] = s[k] + x[k];
     }
-    float best = 0.f;
-    int bi = 0;
-#pragma unroll
-    for (int k = 0; k < CMAX; ++k) {
-      const float v = s[k] / (float)E;
-      if (k < C && (k == 0 || v > best)) {
-        best = v;
-        bi = k;
-      }
-    }
-    fused[pix] = bi;
+    fused[pix] = fuse_argmax_mean<CMAX>(s, (float)E, C);
   }
 }
 

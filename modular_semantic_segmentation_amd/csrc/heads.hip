@@ -5,11 +5,8 @@
 #include "xv_common.h"
 #include "xv_heads.h"
 
-// Floating-point contraction by the SOURCE only (a * b + c inside one expression), never across statements: the fused
-// two-expert head and the unfused path (decoder head -> probability maps -> fusion kernel) must produce the same bits, and
-// under the default -ffp-contract=fast the optimizer fuses a product into a later sum wherever the two happen to meet --
-// round 4: specialising the fused head on the class count removed a select between `p = e * rsum` and `sum += p`, the
-// compiler made it an fma there and not in the kernel that reads p back from memory, and one pixel in a million flipped.
+// Floating-point contraction by the SOURCE only (a * b + c inside one expression), never across statements: the fused heads
+// and the unfused path (decoder head -> probability maps -> fusion kernel) must produce the same bits; see xv_fuse.h.
 #pragma clang fp contract(on)
 
 namespace {
@@ -156,8 +153,9 @@ __global__ __launch_bounds__(256) void decoder_head_label4_kernel(const float* _
 // Replaces, for the default prediction of a two-expert fusion model, two decoder_head launches + the fusion kernel and
 // every per-pixel intermediate between them (Bayes: two int64 label maps written and read back; Dirichlet: two fp32
 // probability maps, 2 x 4C B per pixel each way).  The fusion arithmetic is the one of fusion.hip's kernels, term for
-// term, on the values the unfused path would have stored.  Tables in LDS: tab [2][C][CM], lognorm [2][CM] (Dirichlet),
-// logprior [CM], dec [C][C] (Bayes: the decision per label pair, built by the workgroup).
+// term (staging and fuse_renorm_log shared through xv_fuse.h; the fma chains written out here, see there), on the values
+// the unfused path would have stored.  Tables in LDS: tab [2][C][CM], lognorm [2][CM] (Dirichlet), logprior [CM], dec [C][C]
+// (Bayes: the decision per label pair, built by the workgroup).
 // FULL: the class count IS CM (the 12 classes of the headline model): every `k < C` folds away -- 165 of the Dirichlet
 // form's ~800 vector instructions per pixel were compare-selects on the run-time class count.
 template <int CM, int DIRICHLET, bool FULL = false, int P = (DIRICHLET ? 1 : 4)>
@@ -171,21 +169,10 @@ __global__ __launch_bounds__(256) void fused_head_kernel(const float* __restrict
   float* ln = tab + (DIRICHLET ? 2 * CM * CM : 2 * C * CM);
   float* lp = ln + 2 * CM;
   if constexpr (DIRICHLET) {
-    // transposed: tab[(e CM + k) CM + c] = alpha_e[c][k] - 1, so that the twelve dot products of a pixel advance together,
-    // two classes per v_pk_fma_f32 (below)
-    for (int i = threadIdx.x; i < 2 * CM * CM; i += 256) {
-      const int c = i % CM, k = (i / CM) % CM, e = i / (CM * CM);
-      tab[i] = (c < C && k < C) ? tab_g[(e * C + c) * C + k] : 0.f;
-    }
+    fuse_stage_dirichlet<CM>(tab, ln, tab_g, lognorm_g, 2, C);
   } else {
-    for (int i = threadIdx.x; i < 2 * C * CM; i += 256) {
-      const int k = i % CM, row = i / CM;
-      tab[i] = k < C ? tab_g[row * C + k] : 0.f;
-    }
-  }
-  for (int i = threadIdx.x; i < 2 * CM; i += 256) {
-    const int k = i % CM, e = i / CM;
-    ln[i] = (DIRICHLET && k < C) ? lognorm_g[e * C + k] : 0.f;
+    fuse_stage_rows<CM>(tab, tab_g, 2 * C, C);
+    for (int i = threadIdx.x; i < 2 * CM; i += 256) ln[i] = 0.f;
   }
   if (threadIdx.x < CM) lp[threadIdx.x] = threadIdx.x < C ? logprior_g[threadIdx.x] : 0.f;
   __syncthreads();
@@ -253,21 +240,10 @@ __global__ __launch_bounds__(256) void fused_head_kernel(const float* __restrict
         lab[e][p] = l;
       } else {
         head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < CM; ++k) {
-          sc[k] = k < C ? sc[k] : 0.f;
-          sum += sc[k];
-        }
-        {
-          const float rs = xv_fast_rcp(sum);
-#pragma unroll
-          for (int k = 0; k < CM; ++k) sc[k] = k < C ? xv_fast_log(1e-20f + sc[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
-        }
+        fuse_renorm_log<CM, true>(sc, C);
         // The C dot products sum_k (alpha[c][k] - 1) log p[k], each the fmaf chain over k of dirichlet_fuse_kernel (bit for
         // bit), advanced TWO CLASSES PER INSTRUCTION: v_pk_fma_f32 on the transposed table halves the 2 C^2 = 288 FMAs that
         // made this kernel VALU-bound (padded classes / terms are exact zeros: fma(0, 0, d) = d).
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
         f32x2 dot2[CM / 2];
 #pragma unroll
         for (int cp = 0; cp < CM / 2; ++cp) dot2[cp] = f32x2{0.f, 0.f};
@@ -292,6 +268,7 @@ __global__ __launch_bounds__(256) void fused_head_kernel(const float* __restrict
     if constexpr (!DIRICHLET) {
       out[p] = dec[lab[0][p] * C + lab[1][p]];
     } else {
+      // (fuse_argmax_prior of xv_fuse.h, written out: through it the 20-class forms take 78 / 117 registers for 74 / 81)
       float best = 0.f;
       int bi = 0;
 #pragma unroll
@@ -660,16 +637,11 @@ __global__ __launch_bounds__(256) void fused_dirichlet_head_pk_kernel(const floa
                                                                      const float* __restrict__ lognorm_g,
                                                                      const float* __restrict__ logprior_g,
                                                                      int64_t* __restrict__ fused) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int H2 = CM / 2;
   extern __shared__ __attribute__((aligned(16))) float tab[];  // [2][CM k][CM c] = alpha_e[c][k] - 1, lognorm [2][CM], logprior [CM]
   float* ln = tab + 2 * CM * CM;
   float* lp = ln + 2 * CM;
-  for (int i = threadIdx.x; i < 2 * CM * CM; i += 256) {
-    const int c = i % CM, k = (i / CM) % CM, e = i / (CM * CM);
-    tab[i] = tab_g[(e * CM + c) * CM + k];
-  }
-  for (int i = threadIdx.x; i < 2 * CM; i += 256) ln[i] = lognorm_g[i];
+  fuse_stage_dirichlet<CM>(tab, ln, tab_g, lognorm_g, 2, CM);
   if (threadIdx.x < CM) lp[threadIdx.x] = logprior_g[threadIdx.x];
   __syncthreads();
   const int Ho = Hi * 8, Wo = Wi * 8, Wq = Wo / P;
@@ -809,12 +781,12 @@ __global__ __launch_bounds__(256) void fused_dirichlet_head_pk_kernel(const floa
 //
 // Equal keys of a wave are aggregated before they reach the LDS counters: xv_wave_count (xv_heads.h).
 
-// Dirichlet: per pixel ONCE both experts' log(1e-20 + p) -- head_load_taps / head_eval_taps / head_max / head_softmax and the
-// renormalisation lines of fused_head_kernel<CM, 1>, statement for statement -- then per grid point g the C dot products (the
-// ascending-k fmaf chain of dirichlet_fuse_kernel, two classes per v_pk_fma_f32 on the transposed table as in the fused head),
-// - lognorm, expert 0 + expert 1, + logprior, first-maximum argmax: the label xv_fused_head_fwd gives with point g's tables,
-// bit for bit.  cm[g][label][pred] += 1 for the pixels xv_confusion_matrix counts (0 <= label < C).  LDS: per point the tables
-// [2][CM k][CM c], lognorm [2][CM], logprior [CM], then u32 counters [G][C][C].  A bounded grid, pixels in a grid-stride loop
+// Dirichlet: per pixel ONCE both experts' log(1e-20 + p) -- head_load_taps / head_eval_taps / head_max / head_softmax /
+// fuse_renorm_log, as fused_head_kernel<CM, 1> -- then per grid point g its dot products four classes at a time (the
+// ascending-k fma chain of dirichlet_fuse_kernel, written out: xv_fuse.h says why), - lognorm, expert 0 + expert 1, + logprior,
+// first maximum: the label xv_fused_head_fwd gives with point g's tables, bit for bit.  cm[g][label][pred] += 1 for the pixels
+// xv_confusion_matrix counts (0 <= label < C).  LDS: per point the tables [2][CM k][CM c], lognorm [2][CM], logprior [CM], then
+// u32 counters [G][C][C].  A bounded grid, pixels in a grid-stride loop
 // whose trip count is uniform over the workgroup (xv_wave_count needs whole waves; a lane past the end recomputes the last
 // pixel and counts nothing), one 64-bit global atomic per non-zero cell and workgroup.
 template <int CM>
@@ -826,25 +798,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 
                                                                    const float* __restrict__ logprior_g,
                                                                    const int32_t* __restrict__ labels,
                                                                    unsigned long long* __restrict__ cm) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int PT = 2 * CM * CM + 3 * CM;  // floats per grid point
   extern __shared__ __attribute__((aligned(16))) float gs_tab[];
   uint32_t* cnt = reinterpret_cast<uint32_t*>(gs_tab + G * PT);
-  for (int i = threadIdx.x; i < G * PT; i += 256) {
-    const int g = i / PT, r = i - g * PT;
-    float v;
-    if (r < 2 * CM * CM) {
-      const int c = r % CM, k = (r / CM) % CM, e = r / (CM * CM);
-      v = (c < C && k < C) ? tab_g[((g * 2 + e) * C + c) * C + k] : 0.f;
-    } else if (r < 2 * CM * CM + 2 * CM) {
-      const int q = r - 2 * CM * CM, k = q % CM, e = q / CM;
-      v = k < C ? lognorm_g[(g * 2 + e) * C + k] : 0.f;
-    } else {
-      const int k = r - 2 * CM * CM - 2 * CM;
-      v = k < C ? logprior_g[g * C + k] : 0.f;
-    }
-    gs_tab[i] = v;
-  }
+  fuse_stage_dirichlet_points<CM>(gs_tab, tab_g, lognorm_g, logprior_g, 2, G, C);
   for (int i = threadIdx.x; i < G * C * C; i += 256) cnt[i] = 0u;
   __syncthreads();
   const int Ho = Hi * 8, Wo = Wi * 8;
@@ -873,15 +830,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 
       head_eval_taps<CM>(ta, tb, tc, td, wy1, wy0, wx1, wx0, e == 0 ? ba : bb, C, sc);
       const float m = head_max<CM>(sc, C);
       head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
-      float sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < CM; ++k) {
-        sc[k] = k < C ? sc[k] : 0.f;
-        sum += sc[k];
-      }
-      const float rs = xv_fast_rcp(sum);
-#pragma unroll
-      for (int k = 0; k < CM; ++k) sc[k] = k < C ? xv_fast_log(1e-20f + sc[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
+      fuse_renorm_log<CM, true>(sc, C);
 #pragma unroll
       for (int k2 = 0; k2 < CM / 2; ++k2) lg[e][k2] = f32x2{sc[2 * k2], sc[2 * k2 + 1]};
     }
@@ -1142,13 +1091,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CM <= 16 ? 
 // ---- fused head for two to four experts (bayes_mix.py:33-58, dirichlet_mix.py:14-36,96-136, average_mix.py:18-21) ------------
 // fused_head_kernel / fused_head_average_kernel generalised from two experts to E = 2 .. 4: per output pixel and expert
 // head_load_taps / head_eval_taps / head_max, then head_label_fast + head_softmax (MODE 0) or head_softmax (MODE 1, 2) -- each
-// expert's label / probabilities with the bits decoder_head_kernel stores -- then the statements of fusion.hip's kernels, the
-// experts in ascending order:
-//   MODE 0, Bayes      score[k] = ((tab_0[l_0][k] + tab_1[l_1][k]) + ...) + logprior[k]            (bayes_fuse_kernel)
-//   MODE 1, Dirichlet  renormalise, log(1e-20 + p), the C fmaf chains over k, - lognorm; total = L_0, total += L_1, ...;
-//                      + logprior                                                                   (dirichlet_fuse_kernel)
-//   MODE 2, mean       s = ((p_0 + p_1) + ...), v = s / E (an IEEE division)                        (average_fuse_kernel)
-// and the first maximum.  The labels are those of E decoder heads + xv_bayes_fuse / xv_dirichlet_fuse / xv_average_fuse bit for
+// expert's label / probabilities with the bits decoder_head_kernel stores -- then the fusion of xv_fuse.h, the experts in
+// ascending order:
+//   MODE 0, Bayes      score[k] = ((tab_0[l_0][k] + tab_1[l_1][k]) + ...) + logprior[k], written out   (bayes_fuse_kernel)
+//   MODE 1, Dirichlet  fused_head_kernel<CM, 1>'s statements (written out), fuse_argmax_prior       (dirichlet_fuse_kernel)
+//   MODE 2, mean       s = ((p_0 + p_1) + ...), fuse_argmax_mean                                    (average_fuse_kernel)
+// The labels are those of E decoder heads + xv_bayes_fuse / xv_dirichlet_fuse / xv_average_fuse bit for
 // bit; the E label maps or probability maps between them never exist.  The experts are worked one after another in a loop
 // that is NOT unrolled into the running registers (Bayes: the labels of a pixel packed into one word; Dirichlet: total [CM];
 // mean: s [P][CM]): nothing of size E * C is held, and the register count is the two-expert sibling's whatever E is.  The score
@@ -1192,17 +1140,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_multi_wa
   float* ln = tab + E * rows * CM;
   float* lp = ln + E * CM;
   uint8_t* dec = reinterpret_cast<uint8_t*>(lp + CM);  // [ndec]
-  if constexpr (MODE == 1) {
-    // transposed: tab[(e CM + k) CM + c] = alpha_e[c][k] - 1, two classes per v_pk_fma_f32 (below)
-    for (int i = threadIdx.x; i < E * CM * CM; i += 256) {
-      const int c = i % CM, k = (i / CM) % CM, e = i / (CM * CM);
-      tab[i] = (c < C && k < C) ? tab_g[(e * C + c) * C + k] : 0.f;
-    }
-    for (int i = threadIdx.x; i < E * CM; i += 256) {
-      const int k = i % CM, e = i / CM;
-      ln[i] = k < C ? lognorm_g[e * C + k] : 0.f;
-    }
-  }
+  if constexpr (MODE == 1) fuse_stage_dirichlet<CM>(tab, ln, tab_g, lognorm_g, E, C);
   if constexpr (MODE == 0) {
     for (int i = threadIdx.x; i < E * C * CM; i += 256) {
       const int k = i % CM, row = i / CM;
@@ -1295,20 +1233,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_multi_wa
         for (int k = 0; k < CM; ++k) total[p][k] = e == 0 ? sc[k] : total[p][k] + sc[k];
       } else {
         head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
-        float sum = 0.f;
+        float sum = 0.f;  // (fuse_renorm_log of xv_fuse.h, written out: through it this kernel measured slower, see there)
 #pragma unroll
         for (int k = 0; k < CM; ++k) {
           sc[k] = k < C ? sc[k] : 0.f;
           sum += sc[k];
         }
-        {
-          const float rs = xv_fast_rcp(sum);
+        const float rs = xv_fast_rcp(sum);
 #pragma unroll
-          for (int k = 0; k < CM; ++k) sc[k] = k < C ? xv_fast_log(1e-20f + sc[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
-        }
+        for (int k = 0; k < CM; ++k) sc[k] = k < C ? xv_fast_log(1e-20f + sc[k] * rs) : 0.f;  // renormalise, then log(1e-20 + p)
         // the fmaf chain over k of dirichlet_fuse_kernel per class, two classes per v_pk_fma_f32 on the transposed table
         // (padded classes / terms are exact zeros: fma(0, 0, d) = d), as fused_head_kernel
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
         f32x2 dot2[CM / 2];
 #pragma unroll
         for (int cp = 0; cp < CM / 2; ++cp) dot2[cp] = f32x2{0.f, 0.f};
@@ -1360,17 +1295,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_multi_wa
           }
         }
       }
+    } else if constexpr (MODE == 1) {
+      bi = fuse_argmax_prior<CM>(total[p], lp, C);
     } else {
-      const float fe = (float)E;
-#pragma unroll
-      for (int k = 0; k < CM; ++k) {
-        const float v = MODE == 1 ? total[p][k] + lp[k] : total[p][k] / fe;
-        if (k < C && (k == 0 || v > best)) {
-          best = v;
-          bi = k;
-        }
-      }
+      bi = fuse_argmax_mean<CM>(total[p], (float)E, C);
     }
+    (void)best;
     out[p] = bi;
   }
   int64_t* dst = fused + quad * P;

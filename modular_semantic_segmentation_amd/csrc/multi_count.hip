@@ -4,7 +4,8 @@
 // fused_head_joint_hist_grouped_kernel (grouped_score.hip) are for two experts.  A joint histogram of the experts' labels does
 // not extend (C^(E+1) counters), fusing the pixel under every parameter set and counting in LDS does.
 //
-// Per output pixel and expert ONCE, ascending expert order, statement for statement as fused_head_multi_kernel:
+// Per output pixel and expert ONCE, ascending expert order, statement for statement as fused_head_multi_kernel (written
+// out here, not through xv_fuse.h: see there):
 // head_load_taps / head_eval_taps / head_max, then
 //   MODE 0, Bayes      head_label_fast, head_softmax when it returns -1; after the experts the row sum
 //                      ((tab_0[l_0][k] + tab_1[l_1][k]) + ...) once, and per point + logprior_g[k], first maximum
@@ -58,36 +59,8 @@ constexpr int xv_count_waves(int cm, int mode, int eu) {
 
 // Four experts at 24 classes and more: the taps of a whole expert (4 CM registers) beside three experts' log-probabilities
 // and the scores in work pass the 256 registers a lane can address, so there the taps are loaded and evaluated one class quad
-// at a time (16 registers).
+// at a time (16 registers: head_logits_quads, xv_heads.h).
 constexpr bool xv_count_quads(int cm, int eu) { return eu == 4 && cm >= 24; }
-
-// head_load_taps + head_eval_taps of xv_heads.h a class quad at a time: per class the same fmaf chain on the same four taps,
-// then the same bias -- the same bits.  A quad's loads wait for the quad before (their address depends on its last score: an
-// empty asm, no instruction), otherwise the scheduler asks for all of them at once and nothing is saved.
-template <int CM>
-__device__ __forceinline__ void head_logits_quads(const float* __restrict__ S, const float* __restrict__ bs_g, int n, int iy1,
-                                                  int ix1, int Hi, int Wi, float wy1, float wy0, float wx1, float wx0, int C,
-                                                  float (&sc)[CM]) {
-  const float* p00 = S + (((int64_t)n * (Hi + 2) + iy1) * (Wi + 2) + ix1) * CM;
-  const int64_t rowp = (int64_t)(Wi + 2) * CM;
-  const float w00 = wy0 * wx0, w01 = wy0 * wx1, w10 = wy1 * wx0, w11 = wy1 * wx1;
-#pragma unroll
-  for (int k4 = 0; k4 < CM / 4; ++k4) {
-    int off = 0;
-    if (k4 > 0) asm volatile("" : "+v"(off) : "v"(sc[k4 > 0 ? 4 * k4 - 1 : 0]));
-    const float* p = p00 + off;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p + 4 * k4);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p + CM + 4 * k4);
-    const f32x4 c = *reinterpret_cast<const f32x4*>(p + rowp + 4 * k4);
-    const f32x4 d = *reinterpret_cast<const f32x4*>(p + rowp + CM + 4 * k4);
-    sc[4 * k4] = fmaf(d.x, w11, fmaf(c.x, w10, fmaf(b.x, w01, a.x * w00)));
-    sc[4 * k4 + 1] = fmaf(d.y, w11, fmaf(c.y, w10, fmaf(b.y, w01, a.y * w00)));
-    sc[4 * k4 + 2] = fmaf(d.z, w11, fmaf(c.z, w10, fmaf(b.z, w01, a.z * w00)));
-    sc[4 * k4 + 3] = fmaf(d.w, w11, fmaf(c.w, w10, fmaf(b.w, w01, a.w * w00)));
-  }
-#pragma unroll
-  for (int k = 0; k < CM; ++k) sc[k] += bs_g[k < C ? k : C - 1];
-}
 
 template <int CM, int MODE, int EU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_count_waves(CM, MODE, EU)))) void fused_head_multi_count_kernel(
@@ -95,7 +68,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_count_wa
     const float* __restrict__ lognorm_g, const float* __restrict__ logprior_g, const int32_t* __restrict__ labels,
     const int32_t* __restrict__ group, int NG, int parts, unsigned long long* __restrict__ cm,
     unsigned long long* __restrict__ ecm) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   static_assert(MODE == 1 ? (EU >= 2 && EU <= XV_MULTI_MAXE) : EU == 0, "Dirichlet per expert count, the others rolled");
   const int E = EU > 0 ? EU : E_;
   constexpr int NE = EU > 0 ? EU : 1;          // (array extents of the Dirichlet form)
@@ -174,7 +146,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_count_wa
           const float m = head_max<CM>(sc, C);
           const int le = head_softmax<CM>(sc, m, C);  // sc = the probabilities the unfused path stores
           if (ecm != nullptr) xv_wave_count(ecnt + e * C * C, valid ? l * C + le : -1);
-          float sum = 0.f;
+          float sum = 0.f;  // (fuse_renorm_log of xv_fuse.h, written out: through it this kernel measured slower, see there)
 #pragma unroll
           for (int k = 0; k < CM; ++k) {
             sc[k] = k < C ? sc[k] : 0.f;

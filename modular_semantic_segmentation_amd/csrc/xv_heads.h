@@ -4,9 +4,10 @@
 #pragma once
 
 #include "xv_common.h"
+#include "xv_fuse.h"  // the fusion of a pixel; why equal inputs give equal bits is explained there
 
 // Floating-point contraction by the SOURCE only (a * b + c inside one expression), never across statements, here and in the
-// rest of a file that includes this one: see heads.hip.
+// rest of a file that includes this one: see xv_fuse.h.
 #pragma clang fp contract(on)
 
 // Kernel 2: one thread per output pixel: 4-tap bilinear interpolation of the CM low-resolution class
@@ -29,19 +30,49 @@ __device__ static __forceinline__ void head_load_taps(const float* __restrict__ 
   }
 }
 
-// logits of one output pixel from its taps: explicit fmaf chain (shared by the unfused and the fused head: identical
-// bits by construction), then the bias
+// one class quad of the logits from its four taps: per class an explicit fmaf chain -- the ONE place it is written, so the
+// unfused head, the fused heads and the quad-at-a-time walker below give identical bits by construction
+template <int CM>
+__device__ static __forceinline__ void head_eval_quad(const f32x4& a, const f32x4& b, const f32x4& c, const f32x4& d, float w00,
+                                                      float w01, float w10, float w11, int k4, float (&sc)[CM]) {
+  sc[4 * k4] = fmaf(d.x, w11, fmaf(c.x, w10, fmaf(b.x, w01, a.x * w00)));
+  sc[4 * k4 + 1] = fmaf(d.y, w11, fmaf(c.y, w10, fmaf(b.y, w01, a.y * w00)));
+  sc[4 * k4 + 2] = fmaf(d.z, w11, fmaf(c.z, w10, fmaf(b.z, w01, a.z * w00)));
+  sc[4 * k4 + 3] = fmaf(d.w, w11, fmaf(c.w, w10, fmaf(b.w, w01, a.w * w00)));
+}
+
+// logits of one output pixel from its taps (head_eval_quad per class quad), then the bias
 template <int CM>
 __device__ static __forceinline__ void head_eval_taps(const f32x4 (&a)[CM / 4], const f32x4 (&b)[CM / 4], const f32x4 (&c)[CM / 4],
                                                const f32x4 (&d)[CM / 4], float wy1, float wy0, float wx1, float wx0,
                                                const float* __restrict__ bs_g, int C, float (&sc)[CM]) {
   const float w00 = wy0 * wx0, w01 = wy0 * wx1, w10 = wy1 * wx0, w11 = wy1 * wx1;
 #pragma unroll
+  for (int k4 = 0; k4 < CM / 4; ++k4) head_eval_quad<CM>(a[k4], b[k4], c[k4], d[k4], w00, w01, w10, w11, k4, sc);
+#pragma unroll
+  for (int k = 0; k < CM; ++k) sc[k] += bs_g[k < C ? k : C - 1];
+}
+
+// head_load_taps + head_eval_taps a class quad at a time (16 registers of taps instead of 4 CM; multi_count.hip's wide
+// four-expert forms).  A quad's loads wait for the quad before (their address depends on its last score: an empty asm, no
+// instruction), otherwise the scheduler asks for all of them at once and nothing is saved.
+template <int CM>
+__device__ static __forceinline__ void head_logits_quads(const float* __restrict__ S, const float* __restrict__ bs_g, int n, int iy1,
+                                                         int ix1, int Hi, int Wi, float wy1, float wy0, float wx1, float wx0, int C,
+                                                         float (&sc)[CM]) {
+  const float* p00 = S + (((int64_t)n * (Hi + 2) + iy1) * (Wi + 2) + ix1) * CM;
+  const int64_t rowp = (int64_t)(Wi + 2) * CM;
+  const float w00 = wy0 * wx0, w01 = wy0 * wx1, w10 = wy1 * wx0, w11 = wy1 * wx1;
+#pragma unroll
   for (int k4 = 0; k4 < CM / 4; ++k4) {
-    sc[4 * k4] = fmaf(d[k4].x, w11, fmaf(c[k4].x, w10, fmaf(b[k4].x, w01, a[k4].x * w00)));
-    sc[4 * k4 + 1] = fmaf(d[k4].y, w11, fmaf(c[k4].y, w10, fmaf(b[k4].y, w01, a[k4].y * w00)));
-    sc[4 * k4 + 2] = fmaf(d[k4].z, w11, fmaf(c[k4].z, w10, fmaf(b[k4].z, w01, a[k4].z * w00)));
-    sc[4 * k4 + 3] = fmaf(d[k4].w, w11, fmaf(c[k4].w, w10, fmaf(b[k4].w, w01, a[k4].w * w00)));
+    int off = 0;
+    if (k4 > 0) asm volatile("" : "+v"(off) : "v"(sc[k4 > 0 ? 4 * k4 - 1 : 0]));
+    const float* p = p00 + off;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p + 4 * k4);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(p + CM + 4 * k4);
+    const f32x4 c = *reinterpret_cast<const f32x4*>(p + rowp + 4 * k4);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(p + rowp + CM + 4 * k4);
+    head_eval_quad<CM>(a, b, c, d, w00, w01, w10, w11, k4, sc);
   }
 #pragma unroll
   for (int k = 0; k < CM; ++k) sc[k] += bs_g[k < C ? k : C - 1];
