@@ -34,10 +34,19 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous().numpy()
 
 
+@pytest.fixture
+def default_wgrad_variant_afterwards(ops):
+    """xv_set_wgrad_variant is process-wide: whatever a test that sets it does -- a failed assertion included -- the tests
+    after it run the default kernel again."""
+    yield
+    from modular_semantic_segmentation_amd import _lib
+    _lib.lib().xv_set_wgrad_variant(0)
+
+
 @pytest.mark.parametrize('n,h,w,cin,cout,k', [(2, 16, 32, 64, 64, 3), (1, 24, 40, 128, 64, 3), (2, 6, 10, 64, 128, 3),
                                               (1, 20, 36, 128, 64, 1), (3, 8, 8, 512, 64, 1), (2, 16, 32, 128, 256, 3)])
 @pytest.mark.parametrize('variant', [1, 2, 3])
-def test_conv_filter_and_bias_gradient_exact_on_integers(ops, n, h, w, cin, cout, k, variant):
+def test_conv_filter_and_bias_gradient_exact_on_integers(ops, default_wgrad_variant_afterwards, n, h, w, cin, cout, k, variant):
     from modular_semantic_segmentation_amd import _lib
     assert _lib.lib().xv_set_wgrad_variant(variant) == 0
     rng = np.random.default_rng(cin + cout + h)
