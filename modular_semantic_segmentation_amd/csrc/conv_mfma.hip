@@ -1893,8 +1893,9 @@ extern "C" int xv_conv2d_bwd_data(const xv_act* dy, const void* w_packed_dgrad, 
 extern "C" int xv_conv2d_fwd_residual(const xv_act* x, const void* w_packed, const float* bias,
                                       const xv_act* residual, const xv_act* y, int relu, void* stream) {
   XV_REQUIRE_BF16(x, residual, y);
-  // 1x1 only: those shapes always run on the first-generation kernel, whose epilogue applies the activation before
-  // the addend (the second generation clamps at the store, after it)
+  // 1x1 only: those shapes run on the first-generation kernel or on the flat-GEMM forms (configurations 18 and 23,
+  // conv1x1_gemm.hip), whose epilogues all apply the activation before the addend (the second generation clamps at the
+  // store, after it); tests/test_conv1x1_epilogue_gpu.py holds each of them to that order
   XV_CHECK_ARG(y && y->data && residual && residual->data);
   XV_CHECK_SHAPE(residual->n == y->n && residual->h == y->h && residual->w == y->w && residual->c == y->c);
   return conv_fwd_impl(x, w_packed, bias, y, nullptr, 1, relu, -1, stream, nullptr, (const __bf16*)residual->data);
@@ -2096,6 +2097,8 @@ extern "C" int xv_conv2d_choose_cfg(int n, int h, int w, int cin, int cout, int 
   ConvArgs a{};
   a.N = n, a.H = h, a.W = w, a.Cin = cin, a.Cout = cout;
   a.relu = 1;
+  a.y = const_cast<__bf16*>(sentinel);  // a full-resolution output, as every caller of cfg < 0 but the pooled-only launch has:
+  //                                       the flat-GEMM forms of the 1x1 convs (18, 23) are chosen only with one
   a.num_cus = xv_num_cus();
   a.in_f8 = in_dtype == XV_FP8, a.out_f8 = out_dtype == XV_FP8;
   if (a.in_f8) XV_CHECK_SHAPE((cin & (k == 3 ? 63 : 127)) == 0);

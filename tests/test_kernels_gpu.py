@@ -116,7 +116,8 @@ def test_conv2d_every_tile_configuration(ops, k):
 def test_conv1x1_narrow_gemm(ops, n, h, w, cin):
     """Tile configuration 23 (the FCN's score convs, simple_fcn.py:69-79: 1x1 onto 64 channels): exact on integers, border
     untouched, row counts that are not multiples of the 64-row tile, the library's own choice for this shape, and the
-    same bits as a first-generation tile."""
+    same bits as a first-generation tile.  Bias and relu only: the addend and mask parts of this kernel's epilogue, and
+    their order, are held by tests/test_conv1x1_epilogue_gpu.py."""
     rng = np.random.default_rng(n * h * w + cin)
     x = rng.integers(-2, 3, (n, h, w, cin)).astype(np.float32)
     wt = rng.integers(-1, 2, (1, 1, cin, 64)).astype(np.float32)
@@ -142,8 +143,9 @@ def test_conv1x1_narrow_gemm(ops, n, h, w, cin):
                                             (1, 30, 33, 256, 128), (4, 95, 190, 192, 128), (5, 47, 97, 64, 256),
                                             (3, 96, 191, 128, 384)])
 def test_conv1x1_flat_gemm(ops, n, h, w, cin, cout):
-    """Generation 3 (flat GEMM over the padded rows, cfg 18): exact on integers, with activation + addend + mask in
-    the order of the other kernels, border untouched, row counts that are not multiples of the 128-row tile.  The last three
+    """Generation 3 (flat GEMM over the padded rows, cfg 18): exact on integers with bias and relu (no addend, no mask: those
+    parts of the epilogue, and its order, are held by tests/test_conv1x1_epilogue_gpu.py through xv_conv2d_fwd_residual and
+    xv_conv2d_bwd_data), border untouched, row counts that are not multiples of the 128-row tile.  The last three
     shapes make enough workgroups for the WIDE form of round 6 (256 rows x 128 channels, three stages, conv1x1_gemm_wide_kernel:
     one, three and six K steps; row counts that are not multiples of 256) -- the same bits as generation 1."""
     rng = np.random.default_rng(n * h * w + cin)
