@@ -571,6 +571,41 @@ int xv_fused_head_multi_count_fwd(const float* const* S, const float* const* bia
  * classes and four experts in every mode, within the same 40 KB; 1 in mode 2; 0 outside the supported ranges.  No GPU call. */
 int xv_fused_head_multi_count_capacity(int num_classes, int num_experts, int mode);
 
+/* ---- expert-agreement tables (csrc/agreement.hip) --------------------------------------------------------------------------
+ * What the confusion matrices above cannot say: where the experts disagree, whom the fusion follows, what it loses and what it
+ * rescues.  For E experts (2..4) and C classes (2..32), for every pixel with 0 <= label < C:
+ *   mask       bit e is set iff expert e's label equals the ground truth (0 .. 2^E - 1);
+ *   unanimous  1 iff all E experts give the same label, else 0;
+ *   outcome    0 = the fused label equals the ground truth, 1 = it is wrong and equals at least one expert's label, 2 = it is
+ *              wrong and equals no expert's label;
+ *   table[group][label][mask][unanimous][outcome] += 1, table int64 [num_groups][C][2^E][2][3], accumulated, not cleared.
+ * Cells that cannot occur stay zero (unanimous = 1 with a mask other than 0 or 2^E - 1; mask = 2^E - 1 with unanimous = 0).
+ *
+ * From the experts' low-resolution scores, in one launch: S, bias, num_experts, n, hi, wi, num_classes and mode as
+ * xv_fused_head_multi_count_fwd takes them, with ONE parameter set: mode 0 (Bayes) tab [E][C][C], logprior [C]; mode 1
+ * (Dirichlet) tab [E][C][C] (alpha - 1), lognorm [E][C], logprior [C]; mode 2 (mean) no tables (may be NULL).  Per output pixel
+ * every expert's label is the one xv_decoder_head_fwd gives it and the fused label the one xv_fused_head_multi_fwd writes,
+ * both bit for bit; no label or probability map is written.  labels int32 [n][8hi][8wi].  group (may be NULL, then num_groups
+ * must be 1) int32 [n] in DEVICE memory: a workgroup handles one image at a time and flushes once per image with one 64-bit
+ * atomic per non-zero cell, an id outside [0, num_groups) counts nothing, group g's slice is the ungrouped call on g's images
+ * alone.  max_workgroups bounds the grid (0: the kernel's own bound, two workgroups per CU and never above 512).  XV_EINVAL,
+ * with nothing launched and table untouched, for num_experts outside 2..4, num_classes outside 2..32, an unknown mode,
+ * non-positive sizes, max_workgroups < 0, num_groups < 1 (or not 1 without group), or a null or misaligned pointer the mode
+ * needs (S[e] 16 bytes; table 8; the others their element).                                                                */
+int xv_fused_head_multi_agreement_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                      int num_classes, int mode, const float* tab, const float* lognorm,
+                                      const float* logprior, const int32_t* labels, const int32_t* group, int num_groups,
+                                      int64_t* table, int max_workgroups, void* stream);
+
+/* The same table from MATERIALISED maps, for every model the fused heads do not serve: labels int32 [n][ppi] (n images of ppi
+ * pixels each), expert_labels a host array of num_experts device pointers to int64 [n][ppi] (as xv_bayes_fuse takes `labels`),
+ * fused int64 [n][ppi], group int32 [n] in device memory or NULL.  The same layout, grouping rule, bounds and refusals as
+ * above (XV_EINVAL also for n or ppi below 1); the grid is one workgroup per CU and never above 512.  Only comparisons of the
+ * map values enter a cell's index, so a map value outside [0, C) is counted as a label no class equals.                     */
+int xv_agreement_table(const int32_t* labels, const int64_t* const* expert_labels, int num_experts, const int64_t* fused,
+                       const int32_t* group, int n, int64_t ppi, int num_classes, int num_groups, int64_t* table,
+                       void* stream);
+
 /* Counting form of the fused average head: cm int64 [C][C] (rows = ground truth), cm[label][fused] += 1 over the pixels with
  * 0 <= label < C (labels int32 [n][8hi][8wi], 16-byte aligned) as xv_confusion_matrix would count xv_fused_head_average_fwd's
  * labels: accumulated, not cleared; no label map is written.  max_workgroups bounds the grid (0: the kernel's own bound).

@@ -17,5 +17,8 @@ class AverageFusion(FusionModel):
     def _multi_head(self):
         return lambda *scores: ops.fused_head_multi(*scores, self.config['num_classes'], 'mean')
 
+    def _agreement_head(self):
+        return 'mean', {}
+
     def _fusion(self, expert_outputs, output_attr=None):
         return ops.average_fuse([expert_outputs[m]['prob'] for m in self.modalities])

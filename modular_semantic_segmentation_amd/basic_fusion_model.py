@@ -4,7 +4,8 @@ from copy import deepcopy
 import numpy as np
 import torch
 
-from .base_model import BaseModel, iterate_batches, reduce_over_ranks, score_measures  # noqa: F401
+from .base_model import (BaseModel, grouped_batches, grouped_results, groups_seen, image_groups,  # noqa: F401
+                         iterate_batches, reduce_over_ranks, score_measures)
 from .fcn import FcnEngine, init_variables
 
 
@@ -381,12 +382,82 @@ def grid_results(configs, confusion_matrices):
     return out
 
 
+# ---- expert agreement: who is right and whom the fusion follows (csrc/agreement.hip) ----------------------------------------
+# A confusion matrix is a marginal of one method.  The agreement table keeps, per ground-truth class, what matters of the JOINT
+# of the experts' labels and the fused one: table[label][mask][unanimous][outcome], int64 [C, 2^E, 2, 3], with bit e of mask set
+# iff expert e is right, unanimous = 1 iff all experts give one label, outcome 0 = the fused label is right, 1 = wrong but some
+# expert's label, 2 = wrong and no expert's label.
+
+AGREEMENT_MAX_EXPERTS = 4
+
+
+def _agreement_shares(t, names):
+    """The measures of agreement_measures for K tables at once: t float64 [K, 2^E, 2, 3] -> {key: float64 [K]}; a table
+    without pixels gives NaN."""
+    E = t.shape[1].bit_length() - 1
+    masks = np.arange(t.shape[1])
+    pixels = t.sum((1, 2, 3))
+    split = t[:, :, 0].sum((1, 2))                                      # pixels on which the experts do not all agree
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out = {'pixels': pixels,
+               'fused_accuracy': t[..., 0].sum((1, 2)) / pixels,
+               'expert_accuracy': {names[e]: t[:, (masks >> e) & 1 == 1].sum((1, 2, 3)) / pixels for e in range(E)},
+               'oracle_accuracy': t[:, 1:].sum((1, 2, 3)) / pixels,
+               'unanimous': t[:, :, 1].sum((1, 2)) / pixels,
+               'fused_accuracy_on_disagreement': t[:, :, 0, 0].sum(1) / split,
+               'rescued': t[:, 0, :, 0].sum(1) / pixels,
+               'lost': t[:, 1:, :, 1:].sum((1, 2, 3)) / pixels,
+               'own_way_errors': t[..., 2].sum((1, 2)) / pixels}
+        out['best_expert_accuracy'] = np.max(np.stack(list(out['expert_accuracy'].values())), 0)
+        if E == 2:
+            # the experts differ; expert e alone is right (mask 1 << e): outcome 0 follows e, outcome 1 the other one.  Both
+            # wrong (mask 0): outcome 1 follows one of them, and the table does not say which
+            out['follows'] = {names[e]: (t[:, 1 << e, 0, 0] + t[:, 2 >> e, 0, 1]) / split for e in range(2)}
+            out['follows_undecided'] = t[:, 0, 0, 1] / split
+    return out
+
+
+def agreement_measures(table, modalities=None):
+    """Measures of one expert-agreement table (int [C, 2^E, 2, 3], as score_agreement returns it), pure numpy:
+      pixels                          the pixels counted (0 <= label < C)
+      fused_accuracy                  outcome 0
+      expert_accuracy                 {expert: share of the pixels it labels right}, keyed by `modalities` (else 0 .. E-1)
+      best_expert_accuracy            the largest of them
+      oracle_accuracy                 some expert is right (mask != 0): what a fusion that always picks a right expert reaches
+      unanimous                       all experts give the same label
+      fused_accuracy_on_disagreement  outcome 0 among the pixels with unanimous = 0 (NaN when there are none)
+      rescued                         no expert is right, the fused label is (mask = 0, outcome 0)
+      lost                            some expert is right, the fused label is not (mask != 0, outcome != 0)
+      own_way_errors                  the fused label is wrong and no expert's (outcome 2)
+    all but `pixels` and the disagreement accuracy as shares of the pixels.  Two experts only: `follows`, {expert: share of the
+    non-unanimous pixels on which the fused label equals that expert's}, as far as the table decides it -- where both experts
+    are wrong, differ, and the fusion takes one of the two labels, the table does not say whose: that share is
+    `follows_undecided` and is in neither entry of `follows`.  For three or more experts the table says even less about whom a
+    wrong fused label follows, and both keys are left out.  `per_class`: the same keys per ground-truth class (arrays [C]; a
+    class without pixels gives NaN, as the measures of score() do)."""
+    t = np.asarray(table).astype(np.float64)
+    if t.ndim != 4 or t.shape[2:] != (2, 3) or t.shape[1] not in (4, 8, 16):
+        raise ValueError('agreement table of shape %s, expected [C, 2^E, 2, 3] with E in 2..4' % (t.shape,))
+    E = t.shape[1].bit_length() - 1
+    names = list(modalities) if modalities is not None else list(range(E))
+    if len(names) != E:
+        raise ValueError('%d modalities for a table of %d experts' % (len(names), E))
+
+    def first(v):
+        return {k: first(x) for k, x in v.items()} if isinstance(v, dict) else float(v[0])
+    measures = first(_agreement_shares(t.sum(0, keepdims=True), names))
+    measures['per_class'] = _agreement_shares(t, names)
+    return measures
+
+
 class FusionModel(BaseModel):
     """Mixture of per-modality experts, which this class builds and owns; subclasses implement `_fusion(expert_outputs)` and
     may name a fused head.  config: prefixes {modality: prefix} or modalities (a list: every expert's prefix is its modality,
     dirichlet_mix.py:98), num_units, num_channels {modality: C_in}, expert_model."""
 
     expert_wants = ('classification',)
+    has_fused_score = False         # _fusion(..., output_attr='fused_score') returns the fused class scores
+    agreement_refusal = None        # why score_agreement does not serve the model (the MC-dropout fusions), or None
 
     def __init__(self, name=None, output_dir=None, **config):
         self.modalities = list(config['prefixes'] if 'prefixes' in config else config['modalities'])
@@ -456,3 +527,89 @@ class FusionModel(BaseModel):
             wants = tuple(wants) + ('prob',)
         self.expert_outputs = run_experts(self, batch, wants)
         return self._fusion(self.expert_outputs, output_attr=key)
+
+    # ---- expert agreement on one pass ---------------------------------------------------------------------------------------
+    def _agreement_head(self):
+        """(mode, tables) of ops.fused_head_multi_agreement for this model's fusion -- ('bayes' | 'dirichlet' | 'mean', {tab,
+        lognorm, logprior as that op takes them}) -- or None: the model's agreement is counted from materialised maps only."""
+        return None
+
+    def _count_agreement(self, data, ids, num_groups, max_iterations, scored):
+        """int64 [G, C, 2^E, 2, 3] on the host from ONE pass over `data`.  Where a fused head serves the model (two to four
+        commuted FCN experts, fused_head not switched off) the trunks stop at their low-resolution scores and one
+        ops.fused_head_multi_agreement launch per batch counts; otherwise the experts' label maps are materialised, fused by the
+        model's _fusion and counted by ops.agreement_table.  ids None: one group, every image."""
+        from . import ops
+        C, E = self.config['num_classes'], len(self.modalities)
+        table = torch.zeros((num_groups, C, 1 << E, 2, 3), dtype=torch.int64, device=self.device)
+        head = self._agreement_head()
+        fused_route = head is not None and (fused_head_applicable(self) or multi_head_applicable(self))
+        wants = tuple(dict.fromkeys(tuple(self.expert_wants) + ('classification',)))
+        if ids is None:
+            batches = ((batch, labels, None) for batch, labels in _labelled_batches(self, data, max_iterations))
+        else:
+            batches = grouped_batches(self, data, ids, num_groups, max_iterations, scored)
+        for batch, labels, batch_ids in batches:
+            into = dict(table=table[0]) if batch_ids is None else dict(groups=batch_ids, num_groups=num_groups, table=table)
+            if fused_route:
+                ops.fused_head_multi_agreement(*run_lowres_scores_multi(self, batch), C, head[0], labels, **head[1], **into)
+            else:
+                outs = run_experts(self, batch, wants)
+                fused = self._fusion(outs, output_attr=None)
+                ops.agreement_table(labels, [outs[m]['classification'].contiguous() for m in self.modalities],
+                                    fused.contiguous(), C, **into)
+        reduce_over_ranks(self, table)
+        return table.cpu().numpy()
+
+    def score_agreement(self, data, groups=None, max_iterations=None):
+        """(measures, table) over `data`: the expert-agreement table int64 [C, 2^E, 2, 3] (agreement_measures says what it
+        holds; the experts in the order of self.modalities) from one pass, and its measures.  With `groups` -- one hashable key
+        per image in data order, or 'image', as score_groups takes them, the key table agreed over the ranks the same way --
+        {key: (measures, table)}, each pair what the call returns for the images of that key alone.  Summed over the ranks
+        under reduce_score_over_ranks like the other counting scores.  Two to four experts; the MC-dropout fusions are not
+        served (NotImplementedError)."""
+        if self.agreement_refusal is not None:
+            raise NotImplementedError('%s.score_agreement: %s' % (type(self).__name__, self.agreement_refusal))
+        E = len(self.modalities)
+        if not 2 <= E <= AGREEMENT_MAX_EXPERTS:
+            raise NotImplementedError('score_agreement takes two to %d experts (a table of 2^E masks per class), this model '
+                                      'has %d' % (AGREEMENT_MAX_EXPERTS, E))
+        if groups is None:
+            table = self._count_agreement(data, None, 1, max_iterations, [0])[0]
+            return agreement_measures(table, self.modalities), table
+        data, keys, ids = image_groups(data, groups, max_iterations, self.config['batchsize'],
+                                       across_ranks=self.config.get('reduce_score_over_ranks', False))
+        if not keys:
+            return {}
+        scored = [0]
+        tables = self._count_agreement(data, ids, len(keys), max_iterations, scored)
+        return grouped_results(keys, ids, scored[0], tables, complete=max_iterations is None,
+                               result=lambda t: (agreement_measures(t, self.modalities), np.asarray(t)),
+                               seen=groups_seen(self, ids, scored[0], len(keys)))
+
+    def prediction_difference(self, data):
+        """The fused prediction beside every branch's own (dirichlet_mix.py:275-294, uncertainty_dirichlet_mix.py:424-443), as
+        numpy arrays: {'fused_label' int64 [N,H,W], 'fused_score' float32 [N,H,W,C], and per modality m '<m>_prob' float32
+        [N,H,W,C], '<m>_classification' int64 [N,H,W]}.  The experts' outputs are materialised and fused by the model's own
+        fusion kernel.  'fused_score' is there for the models whose fusion has class scores, BayesFusion and DirichletFusion;
+        AverageFusion (and any model without `has_fused_score`) omits it.  The MC-dropout fusions draw masks per pass and have
+        no fusion of materialised plain outputs: NotImplementedError, as score_agreement."""
+        if self.agreement_refusal is not None:
+            raise NotImplementedError('%s.prediction_difference: %s' % (type(self).__name__, self.agreement_refusal))
+        keys =['fused_label'] + (['fused_score'] if self.has_fused_score else [])
+        keys += ['%s_%s' % (m, k) for m in self.modalities for k in ('prob', 'classification')]
+        parts = {k: [] for k in keys}
+        for batch in self._device_batches(iterate_batches(data, self.config['batchsize']), labels=False):
+            for k, v in self._prediction_difference_batch(batch).items():
+                parts[k].append(v.cpu().numpy())
+        return {k: np.concatenate(v) for k, v in parts.items()}
+
+    def _prediction_difference_batch(self, batch):
+        """One batch of prediction_difference, on the device."""
+        outs = run_experts(self, batch, ('prob', 'classification'))
+        ret = {'fused_label': self._fusion(outs, output_attr=None)}
+        if self.has_fused_score:
+            ret['fused_score'] = self._fusion(outs, output_attr='fused_score')
+        for m in self.modalities:
+            ret['%s_prob' % m], ret['%s_classification' % m] = outs[m]['prob'], outs[m]['classification']
+        return ret

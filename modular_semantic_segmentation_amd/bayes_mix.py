@@ -131,6 +131,13 @@ class BayesFusion(FusionModel):
         return lambda *scores: ops.fused_head_multi(*scores, self.config['num_classes'], 'bayes', tab=self.loglik,
                                                     logprior=self.logprior)
 
+    has_fused_score = True
+
+    def _agreement_head(self):
+        if self.config.get('decision_matrix', False):
+            return None             # as _fused_head: the lookup table decides in float64, the head in float32
+        return 'bayes', dict(tab=self.loglik, logprior=self.logprior)
+
     def _fusion(self, expert_outputs, output_attr=None):
         labels = [expert_outputs[m]['classification'] for m in self.modalities]
         want_score = output_attr == 'fused_score'

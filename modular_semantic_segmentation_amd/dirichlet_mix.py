@@ -117,6 +117,21 @@ class DirichletFusion(FusionModel):
         return lambda *scores: ops.fused_head_multi(*scores, self.config['num_classes'], 'dirichlet', tab=self.am1,
                                                     lognorm=self.lognorm, logprior=self.logprior)
 
+    has_fused_score = True
+
+    def _agreement_head(self):
+        return 'dirichlet', dict(tab=self.am1, lognorm=self.lognorm, logprior=self.logprior)
+
+    def _count_agreement(self, *args, **kwargs):
+        if not hasattr(self, 'am1'):
+            raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
+        return FusionModel._count_agreement(self, *args, **kwargs)
+
+    def _prediction_difference_batch(self, batch):
+        if not hasattr(self, 'am1'):
+            raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
+        return FusionModel._prediction_difference_batch(self, batch)
+
     def _fusion(self, expert_outputs, output_attr=None):
         probs = [expert_outputs[m]['prob'] for m in self.modalities]
         self.probs = dict(zip(self.modalities, probs))

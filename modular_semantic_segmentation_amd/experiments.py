@@ -72,6 +72,24 @@ def evaluate_groups(net, testset, groups, print_results=True, labelinfo=None):
     return results
 
 
+def evaluate_agreement(net, testset, print_results=True):
+    """evaluate() for the question a fusion raises: where do the experts disagree, and whom does the fusion follow there?
+    (net.score_agreement: one pass, the expert-agreement table and its measures.)  Returns (measures, table)."""
+    measures, table = net.score_agreement(testset)
+    if print_results:
+        print('fused accuracy {:.3f} best expert {:.3f} oracle {:.3f}'.format(
+            measures['fused_accuracy'], measures['best_expert_accuracy'], measures['oracle_accuracy']))
+        for expert, accuracy in measures['expert_accuracy'].items():
+            print('{:>15}: {:.3f} accuracy'.format(expert, accuracy))
+        print('experts unanimous on {:.3f} of the pixels, fused accuracy where they are not {:.3f}'.format(
+            measures['unanimous'], measures['fused_accuracy_on_disagreement']))
+        print('rescued {:.4f} lost {:.4f} own-way errors {:.4f}'.format(
+            measures['rescued'], measures['lost'], measures['own_way_errors']))
+        for expert, share in measures.get('follows', {}).items():
+            print('{:>15}: followed on {:.3f} of the disagreements'.format(expert, share))
+    return measures, table
+
+
 def evaluate_on_all_sequences(net, testset, sequence_of_image):
     """experiments/evaluation.py:42-55 (evaluate_on_all_synthia_seqs) on one pass instead of one evaluation per sequence:
     sequence_of_image names the sequence of every image of `testset`, in order.  Returns {sequence: measures}."""

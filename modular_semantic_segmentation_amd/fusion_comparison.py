@@ -51,6 +51,8 @@ class FusionComparison(FusionModel):
             self.class_counts = np.asarray(dirichlet_params['class_counts']).astype('float32')
         FusionModel.__init__(self, 'FusionComparison', output_dir=output_dir, **standard_config)
 
+    agreement_refusal = 'it scores several fusions and predicts with none: ask the fusion model itself'
+
     def _build_graph(self):
         FusionModel._build_graph(self)
         self._build_tables()

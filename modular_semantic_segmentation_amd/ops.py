@@ -850,6 +850,99 @@ def fused_head_multi_count(scores, biases, n, hi, wi, num_classes, mode, labels,
     return cm
 
 
+def _agreement_table_arg(table, groups, n, num_groups, num_classes, num_experts, device):
+    """(table, group ids) of the two agreement ops: int64 [num_groups, C, 2^E, 2, 3], or [C, 2^E, 2, 3] without groups; a zeroed
+    one is made here when none is given."""
+    NG = int(num_groups)
+    ids = None
+    if groups is not None:
+        ids = _group_ids(groups, n, NG, device)
+    elif NG != 1:
+        raise ValueError('num_groups = %d without groups' % NG)
+    shape = ((NG,) if groups is not None else ()) + (int(num_classes), 1 << int(num_experts), 2, 3)
+    if table is None:
+        table = torch.zeros(shape, dtype=torch.int64, device=device)
+    _need(table, torch.int64, 'table')
+    if tuple(table.shape) != shape:
+        raise ValueError('table of shape %s, expected %s' % (tuple(table.shape), shape))
+    return table, ids
+
+
+def fused_head_multi_agreement(scores, biases, n, hi, wi, num_classes, mode, labels, tab=None, lognorm=None, logprior=None,
+                               groups=None, num_groups=1, table=None, max_workgroups=0):
+    """Two to four experts' low-resolution scores (as fused_head_multi takes them, with its tables for `mode`) -> the
+    expert-agreement table against labels (int32 [n, 8hi, 8wi]) in one launch, without a label map:
+    table[label][mask][unanimous][outcome] += 1 over the pixels with 0 <= label < C, where bit e of mask says that expert e's
+    label is right, unanimous that all experts give one label, and outcome is 0 (the fused label is right), 1 (wrong, but some
+    expert's label) or 2 (wrong and no expert's label).  Accumulates into table (int64 [num_groups, C, 2^E, 2, 3], or
+    [C, 2^E, 2, 3] without groups; made here, zeroed, when None) and returns it.  `groups` as fused_head_joint_hist_grouped
+    takes it."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError('unknown fused head mode %r' % (mode,))
+    scores, biases = list(scores), list(biases)
+    if len(scores) != len(biases):
+        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
+    E, C = len(scores), int(num_classes)
+    if not 2 <= E <= 4:
+        raise ValueError('the agreement head takes two to four experts, got %d' % E)
+    cp = (C + 3) // 4 * 4
+    for i, (S, b) in enumerate(zip(scores, biases)):
+        _need(S, torch.float32, 'scores[%d]' % i)
+        _need(b, torch.float32, 'biases[%d]' % i)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+        if b.numel() != C:
+            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
+    _need(labels, torch.int32, 'labels')
+    if labels.numel() != n * hi * wi * 64:
+        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+    if mode == 2:
+        if tab is not None or lognorm is not None or logprior is not None:
+            raise ValueError('the mean takes no tables')
+    else:
+        if tab is None or logprior is None or (mode == 1 and lognorm is None):
+            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
+        if mode == 0 and lognorm is not None:
+            raise ValueError('Bayes fusion takes no lognorm')
+        for name, t, shape in (('tab', tab, (E, C, C)), ('lognorm', lognorm, (E, C)), ('logprior', logprior, (C,))):
+            if t is not None:
+                _need(t, torch.float32, name)
+                if tuple(t.shape) != shape:
+                    raise ValueError('%s of shape %s, expected %s' % (name, tuple(t.shape), shape))
+    table, ids = _agreement_table_arg(table, groups, n, num_groups, C, E, scores[0].device)
+    rc = _lib.lib().xv_fused_head_multi_agreement_fwd(
+        _ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C, int(mode), _ptr(tab), _ptr(lognorm),
+        _ptr(logprior), _ptr(labels), _ptr(ids), int(num_groups), _ptr(table), int(max_workgroups), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_agreement_fwd')
+    return table
+
+
+def agreement_table(labels, expert_labels, fused, num_classes, groups=None, num_groups=1, table=None):
+    """The table of fused_head_multi_agreement from MATERIALISED maps: labels int32 [n, ...], expert_labels a list of two to four
+    int64 maps of that shape (one per expert, in the order of the mask's bits), fused int64 of that shape.  The image axis comes
+    first (it is what `groups` indexes).  Accumulates into table (made here, zeroed, when None) and returns it."""
+    expert_labels = list(expert_labels)
+    E, C = len(expert_labels), int(num_classes)
+    if not 2 <= E <= 4:
+        raise ValueError('the agreement table takes two to four experts, got %d' % E)
+    _need(labels, torch.int32, 'labels')
+    _need(fused, torch.int64, 'fused')
+    if labels.dim() < 2 or labels.numel() == 0:
+        raise ValueError('labels of shape %s, expected non-empty [n, ...]' % (tuple(labels.shape),))
+    for i, lab in enumerate(expert_labels):
+        _need(lab, torch.int64, 'expert_labels[%d]' % i)
+    for name, t in [('fused', fused)] + [('expert_labels[%d]' % i, lab) for i, lab in enumerate(expert_labels)]:
+        if t.shape != labels.shape:
+            raise ValueError('%s of shape %s, labels of shape %s' % (name, tuple(t.shape), tuple(labels.shape)))
+    n = labels.shape[0]
+    table, ids = _agreement_table_arg(table, groups, n, num_groups, C, E, labels.device)
+    rc = _lib.lib().xv_agreement_table(_ptr(labels), _ptr_array(expert_labels), E, _ptr(fused), _ptr(ids), n,
+                                       labels.numel() // n, C, int(num_groups), _ptr(table), _stream())
+    _lib.check(rc, 'xv_agreement_table')
+    return table
+
+
 def fused_head_average_count(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, cm=None, max_workgroups=0):
     """Both experts' low-resolution scores, average-fused and counted against labels (int32 [n, 8hi, 8wi]): accumulates into cm
     (int64 [C,C], rows = ground truth; made here when None) as confusion_matrix would count fused_head_average's labels, and

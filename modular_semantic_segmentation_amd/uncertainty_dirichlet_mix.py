@@ -80,6 +80,9 @@ class UncertaintyMix(DirichletFusion):
         DirichletFusion.__init__(self, output_dir=output_dir, **config)
         self.name = 'UncertaintyMix'
 
+    agreement_refusal = ('every pass draws dropout masks and the plain passes\' labels are not what the uncertainty head fuses: '
+                         'the MC-dropout fusions are not served')
+
     def _build_graph(self):
         FusionModel._build_graph(self)
         self._dropout_seed = mc_dropout_setup('UncertaintyMix', self.config, strict=True, engines=self.experts.values())[2]

@@ -36,6 +36,9 @@ class VarianceFusion(FusionModel):
         standard_config['expert_model'] = 'fcn'
         FusionModel.__init__(self, 'VarianceFusion', output_dir=output_dir, **standard_config)
 
+    agreement_refusal = ('every pass draws dropout masks and the plain passes\' labels are not what the variance head fuses: '
+                         'the MC-dropout fusions are not served')
+
     def _build_graph(self):
         FusionModel._build_graph(self)
         if len(self.modalities) != 2:
