@@ -606,6 +606,41 @@ int xv_agreement_table(const int32_t* labels, const int64_t* const* expert_label
                        const int32_t* group, int n, int64_t ppi, int num_classes, int num_groups, int64_t* table,
                        void* stream);
 
+/* ---- label-tuple heads (csrc/tuple_lut.hip) ----------------------------------------------------------------------------------
+ * For a fusion that sees a pixel only through the tuple of its experts' labels (IBCC: modular_semantic_segmentation_amd/ibcc.py).
+ * S, bias, num_experts (2..4), n, hi, wi and num_classes (2..32) as xv_fused_head_multi_fwd takes them.  The tuple index of a
+ * pixel is t = ((l_0 C + l_1) C + l_2) ..., expert 0 most significant, T = C^E tuples -- the row-major index of a [C]*E
+ * decision array -- where l_e is the label xv_decoder_head_fwd gives expert e for that pixel, bit for bit.
+ *
+ * xv_tuple_capacity: 1 if the three entry points below serve this pair, else 0; no GPU call.  A pair is served when the T
+ * 32-bit counters of the histogram, which stages nothing else, fit the 160 KB of one workgroup's LDS: T <= 40 960 -- every
+ * class count for two and three experts, up to 14 classes for four.                                                          */
+int xv_tuple_capacity(int num_classes, int num_experts);
+
+/* hist int64 [num_groups][T] (8-byte aligned): hist[group[i]][t] += 1 for EVERY output pixel of image i -- no ground truth
+ * enters; accumulated, not cleared.  group (may be NULL, then num_groups must be 1) int32 [n] in DEVICE memory: a workgroup
+ * counts one image at a time in its LDS and flushes once per image with one 64-bit atomic per non-zero cell, an id outside
+ * [0, num_groups) counts nothing, group g's slice is the ungrouped call on g's images alone.  max_workgroups bounds the grid
+ * (0: the kernel's own bound, two workgroups per CU and never above 512).  XV_EINVAL, with nothing launched and hist
+ * untouched, for a null or misaligned pointer, num_experts outside 2..4, num_classes outside 2..32, non-positive sizes,
+ * max_workgroups < 0, num_groups < 1 (or not 1 without group); XV_ESHAPE where xv_tuple_capacity is 0.                        */
+int xv_fused_head_multi_tuple_hist_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                       int num_classes, const int32_t* group, int num_groups, int64_t* hist,
+                                       int max_workgroups, void* stream);
+
+/* lut uint8 [T] in device memory (4-byte aligned), staged once per workgroup in LDS -> fused_label int64 [n][8hi][8wi]
+ * (16-byte aligned) = lut[t]; alignment rules and store shape of xv_fused_head_multi_fwd.  Refusals as above.               */
+int xv_fused_head_multi_lut_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                int num_classes, const uint8_t* lut, int64_t* fused_label, void* stream);
+
+/* Counting form of xv_fused_head_multi_lut_fwd: labels int32 [n][8hi][8wi], cm int64 [num_groups][C][C] (rows = ground
+ * truth), cm[group[i]][label][lut[t]] += 1 over the pixels with 0 <= label < C; accumulated, not cleared; no label map is
+ * written.  A table entry outside [0, C) counts nothing.  group, num_groups, max_workgroups and the refusals as
+ * xv_fused_head_multi_tuple_hist_fwd.                                                                                       */
+int xv_fused_head_multi_lut_count_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                      int num_classes, const uint8_t* lut, const int32_t* labels, const int32_t* group,
+                                      int num_groups, int64_t* cm, int max_workgroups, void* stream);
+
 /* Counting form of the fused average head: cm int64 [C][C] (rows = ground truth), cm[label][fused] += 1 over the pixels with
  * 0 <= label < C (labels int32 [n][8hi][8wi], 16-byte aligned) as xv_confusion_matrix would count xv_fused_head_average_fwd's
  * labels: accumulated, not cleared; no label map is written.  max_workgroups bounds the grid (0: the kernel's own bound).

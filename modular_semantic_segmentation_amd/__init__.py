@@ -14,6 +14,7 @@ def get_model(name):
     from .variance_mix import VarianceFusion
     from .bayesian_fcn import BayesianFCN
     from .uncertainty_dirichlet_mix import UncertaintyMix
+    from .ibcc_mix import IbccFusion
     if name == 'fcn':
         return SimpleFCN
     elif name == 'fusion_fcn':
@@ -32,4 +33,6 @@ def get_model(name):
         return BayesianFCN
     elif name in ['uncertainty_mix', 'uncertainty_fusion']:
         return UncertaintyMix
+    elif name in ['ibcc_fusion', 'ibcc_mix']:
+        return IbccFusion
     raise UserWarning('ERROR: Model %s not found' % name)

@@ -199,6 +199,19 @@ def multi_head_applicable(model):
     return all(isinstance(e, FcnEngine) and e.commuted_head() for e in model.experts.values())
 
 
+def tuple_head_applicable(model):
+    """The label-tuple heads (ops.fused_head_multi_lut, its counting form and ops.fused_head_multi_tuple_hist) serve a fusion
+    that decides by the tuple of its experts' labels (IbccFusion) with two to four FCN experts whose decoder heads are in the
+    commuted form, while the C^E counters of the pair fit one workgroup's LDS (ops.tuple_capacity); config fused_head=False
+    keeps the experts' label maps materialised."""
+    from . import ops
+    if not model.config.get('fused_head', True) or not 2 <= len(model.modalities) <= 4:
+        return False
+    if not all(isinstance(e, FcnEngine) and e.commuted_head() for e in model.experts.values()):
+        return False
+    return ops.tuple_capacity(model.config['num_classes'], len(model.modalities))
+
+
 def run_lowres_scores_multi(model, batch):
     """Every trunk on its own stream (run_trunks without a paired section) up to its low-resolution class scores:
     (scores, biases, n, hi, wi) with one entry per modality, in the model's order -- what ops.fused_head_multi takes."""

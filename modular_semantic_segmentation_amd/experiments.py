@@ -13,7 +13,7 @@ from copy import deepcopy
 import numpy as np
 
 from . import get_model
-from .base_model import score_measures
+from .base_model import iterate_batches, score_measures
 from .basic_fusion_model import parameter_combinations  # noqa: F401  (the reference's name, defined beside score_grid)
 from .bayes_mix import BayesFusion
 from .dirichlet_mix import DirichletFusion
@@ -194,6 +194,53 @@ def fit_and_evaluate_bayes_fusion(net_config, data_description, measure_set, tes
     with BayesFusion(data_description=data_description, confusion_matrices=confusion_matrices, **net_config) as net:
         import_weights_into_network(net, starting_weights)
         info['measurements']['fusion'], info['confusion_matrix'] = net.score(test_set)
+    return info
+
+
+def collect_predictions(net, measure_set, test_set, save_to):
+    """experiments/ibcc_fusion.py:18-42: every expert's label maps on both halves and the ground truth, written as
+    `predictions.npz` under `save_to` -- the file an external IBCC reads.  Keys: measure_<modality>, test_<modality> (int64
+    [N,H,W]), measure_gt, test_gt (the sets' own labels).  net: a fusion model (its experts are run once per half, through its
+    `expert_outputs`, with the fused head off so that they are materialised).  Returns the file's path."""
+    import os
+    predictions = {}
+    fused_head = net.config.get('fused_head', True)
+    net.config['fused_head'] = False
+    try:
+        for part, data in (('measure', measure_set), ('test', test_set)):
+            maps = {m: [] for m in net.modalities}
+            for batch in iterate_batches(data, net.config['batchsize']):
+                net.predict(batch)
+                for m in net.modalities:
+                    label = net.expert_outputs[m]['classification']
+                    maps[m].append(np.asarray(label.cpu() if hasattr(label, 'cpu') else label).astype(np.int64))
+            for m in net.modalities:
+                predictions['%s_%s' % (part, m)] = np.concatenate(maps[m])
+            predictions['%s_gt' % part] = np.asarray(data['labels']) if isinstance(data, dict) else \
+                np.stack([np.asarray(sample['labels']) for sample in data])
+    finally:
+        net.config['fused_head'] = fused_head
+    os.makedirs(save_to, exist_ok=True)
+    path = os.path.join(save_to, 'predictions.npz')
+    np.savez_compressed(path, **predictions)
+    return path
+
+
+def fit_and_evaluate_ibcc(net_config, data_description, measure_set, test_set, starting_weights, adapt_set=None):
+    """The IBCC counterpart of fit_and_evaluate_bayes_fusion: every expert's confusion matrix from ONE pass of the experts
+    over the measurement set (IbccFusion.measure), then the fusion with those priors scored on the test set twice -- by its
+    priors alone, and after adapt() on `adapt_set` (default: the test set's images; its labels are never read).  Returns {'confusion_matrices', 'prior': (measures, cm), 'adapted': (measures, cm), 'ibcc': the
+    adaptation's ibcc.IbccResult}."""
+    from .ibcc_mix import IbccFusion
+    info = {}
+    C = data_description[2]
+    flat = {m: np.ones((C, C)) for m in net_config['prefixes']}          # flat priors until the experts are measured
+    with IbccFusion(data_description=data_description, confusion_matrices=flat, **net_config) as net:
+        import_weights_into_network(net, starting_weights)
+        info['confusion_matrices'] = net.measure(measure_set)
+        info['prior'] = net.score(test_set)
+        info['ibcc'] = net.adapt(test_set if adapt_set is None else adapt_set)
+        info['adapted'] = net.score(test_set)
     return info
 
 

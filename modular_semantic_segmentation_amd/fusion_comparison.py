@@ -40,6 +40,10 @@ class FusionComparison(FusionModel):
     def __init__(self, output_dir=None, confusion_matrices=None, dirichlet_params=None, **config):
         standard_config = {'learning_rate': 0.0, 'class_prior': 'data'}
         standard_config.update(config)
+        for key in ('prior_strength', 'ibcc_max_iter', 'ibcc_tol'):
+            if key in standard_config:
+                raise NotImplementedError('FusionComparison has no IBCC row (config key %r): an IBCC fusion adapts to the data '
+                                          'it scores, the rows here are frozen after fit(); score an IbccFusion itself' % key)
         for key in ('sigma', 'delta', 'beta'):
             if key not in standard_config:
                 raise UserWarning('ERROR: FusionComparison needs %s (the Dirichlet fusion\'s parameter)' % key)

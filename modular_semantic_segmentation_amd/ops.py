@@ -943,6 +943,106 @@ def agreement_table(labels, expert_labels, fused, num_classes, groups=None, num_
     return table
 
 
+# ---- label-tuple heads (csrc/tuple_lut.hip): the tuple of a pixel's expert labels is t = ((l_0 C + l_1) C + l_2) ..., expert
+# 0 most significant: the row-major index of a [C]*E decision array
+
+def tuple_capacity(num_classes, num_experts):
+    """Do the three label-tuple heads serve this pair (C^E u32 counters within one workgroup's LDS)?  No GPU call."""
+    return bool(_lib.lib().xv_tuple_capacity(int(num_classes), int(num_experts)))
+
+
+def _check_tuple_experts(scores, biases, n, hi, wi, num_classes, what):
+    """(scores, biases, E, C, T) of a label-tuple head, the shapes checked as fused_head_multi checks them."""
+    scores, biases = list(scores), list(biases)
+    if len(scores) != len(biases):
+        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
+    E, C = len(scores), int(num_classes)
+    if not 2 <= E <= 4:
+        raise ValueError('%s takes two to four experts, got %d' % (what, E))
+    cp = (C + 3) // 4 * 4
+    for i, (S, b) in enumerate(zip(scores, biases)):
+        _need(S, torch.float32, 'scores[%d]' % i)
+        _need(b, torch.float32, 'biases[%d]' % i)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+        if b.numel() != C:
+            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
+    if not 2 <= C <= 32 or not tuple_capacity(C, E):
+        raise ValueError('%s does not serve %d experts at %d classes (tuple_capacity)' % (what, E, C))
+    return scores, biases, E, C, C ** E
+
+
+def _check_tuple_lut(lut, T):
+    _need(lut, torch.uint8, 'lut')
+    if tuple(lut.shape) != (T,):
+        raise ValueError('lut of shape %s, expected %s' % (tuple(lut.shape), (T,)))
+
+
+def _grouped_output(out, name, groups, n, num_groups, cell_shape, device):
+    """(out, group ids) of a grouped counting op: int64 [num_groups, *cell_shape], or cell_shape without groups; a zeroed one
+    is made here when none is given."""
+    NG = int(num_groups)
+    ids = None
+    if groups is not None:
+        ids = _group_ids(groups, n, NG, device)
+    elif NG != 1:
+        raise ValueError('num_groups = %d without groups' % NG)
+    shape = ((NG,) if groups is not None else ()) + tuple(cell_shape)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.int64, device=device)
+    _need(out, torch.int64, name)
+    if tuple(out.shape) != shape:
+        raise ValueError('%s of shape %s, expected %s' % (name, tuple(out.shape), shape))
+    return out, ids
+
+
+def fused_head_multi_tuple_hist(scores, biases, n, hi, wi, num_classes, groups=None, num_groups=1, hist=None,
+                                max_workgroups=0):
+    """Two to four experts' low-resolution scores (as fused_head_multi takes them) -> the histogram of their label tuples over
+    EVERY output pixel, in one launch and without a label map or ground truth: hist[t] += 1.  Accumulates into hist (int64
+    [num_groups, C^E], or [C^E] without groups; made here, zeroed, when None) and returns it.  `groups` as
+    fused_head_joint_hist_grouped takes it."""
+    scores, biases, E, C, T = _check_tuple_experts(scores, biases, n, hi, wi, num_classes, 'the tuple histogram')
+    hist, ids = _grouped_output(hist, 'hist', groups, n, num_groups, (T,), scores[0].device)
+    rc = _lib.lib().xv_fused_head_multi_tuple_hist_fwd(_ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C,
+                                                      _ptr(ids), int(num_groups), _ptr(hist), int(max_workgroups), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_tuple_hist_fwd')
+    return hist
+
+
+def fused_head_multi_lut(scores, biases, n, hi, wi, num_classes, lut, out=None):
+    """Two to four experts' low-resolution scores -> the label map (int64 [n, 8hi, 8wi]) a lookup table over their label
+    tuples decides, lut uint8 [C^E], in one launch: out = lut[t]."""
+    scores, biases, E, C, T = _check_tuple_experts(scores, biases, n, hi, wi, num_classes, 'the lookup head')
+    _check_tuple_lut(lut, T)
+    if out is None:
+        out = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.int64, device=scores[0].device)
+    elif out.dtype != torch.int64 or out.numel() != n * hi * wi * 64:
+        raise ValueError('out must be int64 of %d elements' % (n * hi * wi * 64))
+    rc = _lib.lib().xv_fused_head_multi_lut_fwd(_ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C,
+                                               _ptr(lut), _ptr(out), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_lut_fwd')
+    return out
+
+
+def fused_head_multi_lut_count(scores, biases, n, hi, wi, num_classes, lut, labels, groups=None, num_groups=1, cm=None,
+                               max_workgroups=0):
+    """Counting form of fused_head_multi_lut: cm[label][lut[t]] += 1 over the pixels with 0 <= label < C (labels int32
+    [n, 8hi, 8wi]), without a label map.  Accumulates into cm (int64 [num_groups, C, C], or [C, C] without groups; made here,
+    zeroed, when None) and returns it."""
+    scores, biases, E, C, T = _check_tuple_experts(scores, biases, n, hi, wi, num_classes, 'the counting lookup head')
+    _check_tuple_lut(lut, T)
+    _need(labels, torch.int32, 'labels')
+    if labels.numel() != n * hi * wi * 64:
+        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+    cm, ids = _grouped_output(cm, 'cm', groups, n, num_groups, (C, C), scores[0].device)
+    rc = _lib.lib().xv_fused_head_multi_lut_count_fwd(_ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C,
+                                                     _ptr(lut), _ptr(labels), _ptr(ids), int(num_groups), _ptr(cm),
+                                                     int(max_workgroups), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_lut_count_fwd')
+    return cm
+
+
 def fused_head_average_count(Sa, Sb, bias_a, bias_b, n, hi, wi, num_classes, labels, cm=None, max_workgroups=0):
     """Both experts' low-resolution scores, average-fused and counted against labels (int32 [n, 8hi, 8wi]): accumulates into cm
     (int64 [C,C], rows = ground truth; made here when None) as confusion_matrix would count fused_head_average's labels, and
