@@ -606,6 +606,52 @@ int xv_agreement_table(const int32_t* labels, const int64_t* const* expert_label
                        const int32_t* group, int n, int64_t ppi, int num_classes, int num_groups, int64_t* table,
                        void* stream);
 
+/* ---- calibration scoring (csrc/calibration.hip) ------------------------------------------------------------------------------
+ * Can the confidence of a posterior be believed?  For a pixel with class scores s[k], k < C (2..32), in the log domain -- the
+ * fused score xv_bayes_fuse / xv_dirichlet_fuse write to score_out; for the mean ln(1e-20 + mean_e p_e[k]); for one expert its
+ * logits -- `win` is the first maximum of s (the label the existing route writes; a temperature never moves it) and, per
+ * temperature T > 0,
+ *   z = sum_k exp((s[k] - s[win]) / T), conf = 1 / z (IEEE divisions), q = (uint32)(conf 2^24) (truncation, q <= 2^24),
+ *   bin = min(q >> (24 - bin_bits), NB - 1) with NB = 1 << bin_bits, correct = (win == label),
+ *   nll_pixel = min(ln z - (s[label] - s[win]) / T, -ln 1e-10)                       (the clip of xv_uncertainty_stats).
+ * Over the pixels with 0 <= label < C: table int64 [num_groups][num_temperatures][NB][3], table[g][t][bin] += (1, correct, q),
+ * and nll double [num_groups][num_temperatures] += nll_pixel; both accumulated, not cleared.  The three columns are integers:
+ * groups, ranks and repeated launches add exactly; the mean confidence of a bin is its q sum / count / 2^24.
+ *
+ * xv_calibration_capacity: temperatures one launch serves with num_tables tables per temperature (1: the fusion alone; 1 + E:
+ * the experts' tables beside it) in one workgroup's 160 KB of LDS, of which 20 KB stay with the fusion tables: a cell is 16
+ * bytes (the q sum is 64 bits wide), a table 16 NB bytes and 256 bytes of NLL sums, and a launch takes at most 16 temperatures:
+ * min(16, 140 KB / (num_tables (16 NB + 256))).  0 for bin_bits outside 4..10 or num_tables outside 1..5.  No GPU call.       */
+int xv_calibration_capacity(int bin_bits, int num_tables);
+
+/* The table from a MATERIALISED map: values float32 [n][ppi][C] (n images of ppi pixels each; 4-byte aligned), kind 0 = class
+ * scores, kind 1 = probabilities, mapped to ln(1e-20 + p) after `win` is taken as their first maximum; labels int32 [n][ppi];
+ * group (may be NULL, then num_groups must be 1) int32 [n] in DEVICE memory; temperatures a HOST array of num_temperatures
+ * floats.  A workgroup handles one image at a time and flushes once per image with one 64-bit atomic per non-zero column of a
+ * non-empty bin; an id outside [0, num_groups) counts nothing; group g's slice is the ungrouped call on g's images alone; the
+ * grid is two workgroups per CU and never above 512.  XV_EINVAL, with nothing launched and the outputs untouched, for bin_bits
+ * outside 4..10, num_temperatures < 1 or above xv_calibration_capacity(bin_bits, 1), a temperature that is not finite and
+ * positive, num_classes outside 2..32, an unknown kind, n or ppi below 1, num_groups < 1 (or not 1 without group), or a null
+ * or misaligned pointer (table and nll 8 bytes; the others their element).                                                    */
+int xv_calibration_table(const float* values, int kind, const int32_t* labels, const int32_t* group, int n, int64_t ppi,
+                         int num_classes, const float* temperatures, int num_temperatures, int bin_bits, int num_groups,
+                         int64_t* table, double* nll, void* stream);
+
+/* The table from the experts' low-resolution scores, in one launch: S, bias, num_experts (2..4), n, hi, wi, num_classes, mode
+ * (0 Bayes, 1 Dirichlet, 2 mean), tab, lognorm, logprior, labels, group, num_groups and max_workgroups as
+ * xv_fused_head_multi_agreement_fwd takes them, one parameter set.  The fused scores are those of the fusion kernels on the
+ * maps xv_decoder_head_fwd writes, `win` the label xv_fused_head_multi_fwd writes.  expert_table int64
+ * [num_groups][E][num_temperatures][NB][3] and expert_nll double [num_groups][E][num_temperatures] (both NULL, or both given)
+ * take each expert's own table from its interpolated logits at the same temperatures.  No label, score or probability map is
+ * written.  XV_EINVAL, with nothing launched and every output untouched, as above (the capacity is that of 1 + E tables with
+ * expert_table) and as xv_fused_head_multi_agreement_fwd refuses.                                                             */
+int xv_fused_head_multi_calibration_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                        int num_classes, int mode, const float* tab, const float* lognorm,
+                                        const float* logprior, const int32_t* labels, const int32_t* group, int num_groups,
+                                        const float* temperatures, int num_temperatures, int bin_bits, int64_t* table,
+                                        double* nll, int64_t* expert_table, double* expert_nll, int max_workgroups,
+                                        void* stream);
+
 /* ---- label-tuple heads (csrc/tuple_lut.hip) ----------------------------------------------------------------------------------
  * For a fusion that sees a pixel only through the tuple of its experts' labels (IBCC: modular_semantic_segmentation_amd/ibcc.py).
  * S, bias, num_experts (2..4), n, hi, wi and num_classes (2..32) as xv_fused_head_multi_fwd takes them.  The tuple index of a

@@ -1,4 +1,6 @@
 """Average fusion (reference: xview/models/average_mix.py)."""
+import torch
+
 from . import ops
 from .basic_fusion_model import FusionModel
 
@@ -19,6 +21,15 @@ class AverageFusion(FusionModel):
 
     def _agreement_head(self):
         return 'mean', {}
+
+    def _calibration_values(self, expert_outputs):
+        # the mean probabilities average_fuse decides by: ((p_0 + p_1) + ...) / E, the division by a device tensor so that it
+        # is an IEEE division per element, as the kernels divide (a host scalar would become a product with 1 / E)
+        probs = [expert_outputs[m]['prob'] for m in self.modalities]
+        total = probs[0]
+        for p in probs[1:]:
+            total = total + p
+        return total / torch.tensor(float(len(probs)), dtype=torch.float32, device=total.device), 1
 
     def _fusion(self, expert_outputs, output_attr=None):
         return ops.average_fuse([expert_outputs[m]['prob'] for m in self.modalities])

@@ -431,6 +431,104 @@ class BaseModel(object):
         return grouped_results(keys, ids, scored[0], counts, complete=max_iterations is None,
                                seen=groups_seen(self, ids, scored[0], len(keys)))
 
+    # ---- calibration: can the confidence be believed? (csrc/calibration.hip, calibration.py) --------------------------------
+    calibration_refusal = None      # why score_calibration does not serve the model, or None
+
+    def _calibration_refusal(self):
+        return self.calibration_refusal
+
+    def _calibration_experts(self):
+        """The names of the experts whose own tables score_calibration(experts=True) returns (a fusion model's modalities)."""
+        raise ValueError('%s has no experts: experts=True is a fusion model\'s' % type(self).__name__)
+
+    def _calibrate_batch(self, batch, labels, temps, bin_bits, into, expert_into):
+        """One batch of the calibration pass: the model's class scores, materialised, counted by ops.calibration_table into
+        `into` (table, nll and, grouped, groups and num_groups, as that op takes them).  A fusion model overrides it."""
+        from . import ops
+        score = self._predict_batch_impl(batch, output_attr='score')
+        C = self.config['num_classes']
+        if score.dtype != torch.float32 or score.dim() != labels.dim() + 1 or score.shape[-1] != C:
+            raise NotImplementedError('%s.score_calibration: the model has no class-score output' % type(self).__name__)
+        ops.calibration_table(score.contiguous(), labels, temps, bin_bits, kind=0, **into)
+
+    def _count_calibration(self, data, temps, bin_bits, ids, num_groups, max_iterations, scored, experts):
+        """(table int64 [G, T, NB, 3], nll float64 [G, T], expert tables [G, E, T, NB, 3] and NLL sums [G, E, T] or None) on
+        the host from ONE eager pass over `data`; ids None: one group, every image."""
+        refusal = self._calibration_refusal()
+        if refusal is not None:
+            raise NotImplementedError('%s.score_calibration: %s' % (type(self).__name__, refusal))
+        NT, NB = len(temps), 1 << int(bin_bits)
+        table = torch.zeros((num_groups, NT, NB, 3), dtype=torch.int64, device=self.device)
+        nll = torch.zeros((num_groups, NT), dtype=torch.float64, device=self.device)
+        etab = enll = None
+        if experts:
+            E = len(self._calibration_experts())
+            etab = torch.zeros((num_groups, E, NT, NB, 3), dtype=torch.int64, device=self.device)
+            enll = torch.zeros((num_groups, E, NT), dtype=torch.float64, device=self.device)
+        if ids is None:
+            batches = ((batch, self._to_device(batch['labels'], torch.int32), None) for batch in self._device_batches(
+                iterate_batches(data, self.config['batchsize'], max_iterations), labels=True))
+        else:
+            batches = grouped_batches(self, data, ids, num_groups, max_iterations, scored)
+        for batch, labels, batch_ids in batches:
+            if batch_ids is None:
+                into = dict(table=table[0], nll=nll[0])
+                expert_into = dict(expert_table=etab[0], expert_nll=enll[0]) if experts else None
+            else:
+                into = dict(groups=batch_ids, num_groups=num_groups, table=table, nll=nll)
+                expert_into = dict(expert_table=etab, expert_nll=enll) if experts else None
+            self._calibrate_batch(batch, labels, temps, bin_bits, into, expert_into)
+        reduce_over_ranks(self, *([table, nll] + ([etab, enll] if experts else [])))
+        host = [t.cpu().numpy() if t is not None else None for t in (table, nll, etab, enll)]
+        return tuple(host)
+
+    def _calibration_results(self, counts, g, t, num_bins, experts):
+        """What score_calibration returns for group g at temperature index t."""
+        from .calibration import calibration_measures
+        table, nll, etab, enll = counts
+        ret = (calibration_measures(table[g, t], nll[g, t], num_bins), table[g, t])
+        if experts:
+            ret += ({m: (calibration_measures(etab[g, e, t], enll[g, e, t], num_bins), etab[g, e, t])
+                     for e, m in enumerate(self._calibration_experts())},)
+        return ret
+
+    def score_calibration(self, data, temperature=1.0, groups=None, max_iterations=None, bin_bits=10, num_bins=15,
+                          experts=False):
+        """(measures, table) over `data`: the reliability table int64 [NB, 3] of the model's posterior at `temperature` --
+        per confidence bin (NB = 1 << bin_bits of them) the pixels, the correct ones and the sum of their confidence in steps
+        of 2^-24, over the pixels with a valid label -- and calibration.calibration_measures of it on `num_bins` bins: ECE,
+        MCE, accuracy, mean_confidence, overconfidence, NLL and the diagram.  The confidence is that of the class scores the
+        model decides by (a fusion: its fused scores; the mean fusion: its mean probabilities), softened by the temperature;
+        the label never changes.  With `groups` -- one hashable key per image in data order, or 'image', as score_groups takes
+        them -- {key: (measures, table)}.  experts=True (fusion models): a third entry {modality: (measures, table)}, every
+        expert's own table from the same pass.  Summed over the ranks under reduce_score_over_ranks like the other counting
+        scores; the pass runs eagerly.  A model without class scores raises NotImplementedError."""
+        temps = [float(temperature)]
+        if groups is None:
+            counts = self._count_calibration(data, temps, bin_bits, None, 1, max_iterations, [0], experts)
+            return self._calibration_results(counts, 0, 0, num_bins, experts)
+        refusal = self._calibration_refusal()
+        if refusal is not None:
+            raise NotImplementedError('%s.score_calibration: %s' % (type(self).__name__, refusal))
+        data, keys, ids = image_groups(data, groups, max_iterations, self.config['batchsize'],
+                                       across_ranks=self.config.get('reduce_score_over_ranks', False))
+        if not keys:
+            return {}
+        scored = [0]
+        counts = self._count_calibration(data, temps, bin_bits, ids, len(keys), max_iterations, scored, experts)
+        return grouped_results(keys, ids, scored[0], np.arange(len(keys)), complete=max_iterations is None,
+                               result=lambda g: self._calibration_results(counts, int(g), 0, num_bins, experts),
+                               seen=groups_seen(self, ids, scored[0], len(keys)))
+
+    def calibration_search(self, data, temperatures, max_iterations=None, bin_bits=10, num_bins=15):
+        """Every temperature of `temperatures` on ONE pass over `data`: {'temperatures': the list, 'measures': [what
+        score_calibration returns first, per temperature], 'tables': int64 [T, NB, 3], 'best': the temperature of least NLL}."""
+        from .calibration import best_temperature
+        temps = [float(t) for t in temperatures]
+        counts = self._count_calibration(data, temps, bin_bits, None, 1, max_iterations, [0], False)
+        measures = [self._calibration_results(counts, 0, t, num_bins, False)[0] for t in range(len(temps))]
+        return {'temperatures': temps, 'measures': measures, 'tables': counts[0][0], 'best': best_temperature(temps, measures)}
+
     # ---- weights ----------------------------------------------------------------------------------------
     def _variables_changed(self):
         """Called after self.variables was modified; subclasses re-upload to the GPU.  The engines allocate

@@ -600,6 +600,48 @@ class FusionModel(BaseModel):
                                result=lambda t: (agreement_measures(t, self.modalities), np.asarray(t)),
                                seen=groups_seen(self, ids, scored[0], len(keys)))
 
+    # ---- calibration of the fused posterior on one pass (BaseModel.score_calibration, csrc/calibration.hip) ----------------
+    def _calibration_refusal(self):
+        return self.calibration_refusal if self.calibration_refusal is not None else self.agreement_refusal
+
+    def _calibration_experts(self):
+        return self.modalities
+
+    def _calibration_values(self, expert_outputs):
+        """(values float32 [N, H, W, C], kind) of the materialised route: the fused class scores in the log domain (kind 0) --
+        the model's fusion with output_attr='fused_score' -- or, kind 1, the probabilities it decides by (AverageFusion)."""
+        if not self.has_fused_score:
+            raise NotImplementedError('%s.score_calibration: the fusion has no class scores' % type(self).__name__)
+        return self._fusion(expert_outputs, output_attr='fused_score'), 0
+
+    def _calibrate_batch(self, batch, labels, temps, bin_bits, into, expert_into):
+        """Where a fused head serves the model (two to four commuted FCN experts, fused_head not switched off) the trunks stop
+        at their low-resolution scores and ONE ops.fused_head_multi_calibration launch counts the fused table and, on request,
+        every expert's; otherwise the experts' outputs are materialised, fused by the model's own kernel with its score output
+        and counted by ops.calibration_table, every expert's table from its materialised class scores."""
+        from . import ops
+        C = self.config['num_classes']
+        head = self._agreement_head()
+        if head is not None and (fused_head_applicable(self) or multi_head_applicable(self)):
+            ops.fused_head_multi_calibration(*run_lowres_scores_multi(self, batch), C, head[0], labels, temps, bin_bits,
+                                             **head[1], **into, **(expert_into or {}))
+            return
+        wants = tuple(dict.fromkeys(tuple(self.expert_wants) + (('score',) if expert_into else ())))
+        outs = run_experts(self, batch, wants)
+        values, kind = self._calibration_values(outs)
+        ops.calibration_table(values.contiguous(), labels, temps, bin_bits, kind=kind, **into)
+        if expert_into:
+            grouped = 'groups' in into
+            for e, m in enumerate(self.modalities):
+                # (a grouped expert table [G, E, T, NB, 3] has no dense slice per expert: counted apart, then added)
+                part, part_nll = ops.calibration_table(
+                    outs[m]['score'].contiguous(), labels, temps, bin_bits, kind=0,
+                    **(dict(groups=into['groups'], num_groups=into['num_groups']) if grouped else
+                       dict(table=expert_into['expert_table'][e], nll=expert_into['expert_nll'][e])))
+                if grouped:
+                    expert_into['expert_table'][:, e] += part
+                    expert_into['expert_nll'][:, e] += part_nll
+
     def prediction_difference(self, data):
         """The fused prediction beside every branch's own (dirichlet_mix.py:275-294, uncertainty_dirichlet_mix.py:424-443), as
         numpy arrays: {'fused_label' int64 [N,H,W], 'fused_score' float32 [N,H,W,C], and per modality m '<m>_prob' float32

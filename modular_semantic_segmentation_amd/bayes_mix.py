@@ -138,6 +138,11 @@ class BayesFusion(FusionModel):
             return None             # as _fused_head: the lookup table decides in float64, the head in float32
         return 'bayes', dict(tab=self.loglik, logprior=self.logprior)
 
+    def _calibration_refusal(self):
+        if self.config.get('decision_matrix', False):
+            return 'decision_matrix=True fuses by a lookup table, which has no class scores to take a confidence from'
+        return FusionModel._calibration_refusal(self)
+
     def _fusion(self, expert_outputs, output_attr=None):
         labels = [expert_outputs[m]['classification'] for m in self.modalities]
         want_score = output_attr == 'fused_score'

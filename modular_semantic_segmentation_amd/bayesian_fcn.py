@@ -87,6 +87,9 @@ class BayesianFCN(UncertaintyModel, SimpleFCN):
     def _graph_capturable(self):
         return False
 
+    calibration_refusal = ('every pass draws dropout masks and the model decides by the mean of its samples, not by one '
+                           'pass\'s class scores: its confidence is scored by the uncertainty benchmarks (nll_score, temperature_search)')
+
     def fit(self, *args, **kwargs):
         raise NotImplementedError('BayesianFCN is inference only: training with dropout (masks in the forward pass and their '
                                   "gradient in the trainer) is not implemented; train get_model('fcn') and import its weights")

@@ -90,6 +90,27 @@ def evaluate_agreement(net, testset, print_results=True):
     return measures, table
 
 
+def evaluate_calibration(net, testset, temperatures=None, print_results=True):
+    """evaluate() for the question a probabilistic fusion raises: can its confidence be believed, and is it more over-confident
+    than its experts?  (net.score_calibration: one pass, the reliability tables of the fusion and of every expert.)  Prints
+    accuracy, mean confidence, ECE and NLL per expert and for the fusion; with a list of `temperatures` also the temperature of
+    least NLL on the fused posterior (net.calibration_search: one more pass) and the measures there.  Returns what
+    score_calibration returns, with the calibration_search result as a last entry when temperatures are given."""
+    has_experts = bool(getattr(net, 'modalities', None))
+    result = net.score_calibration(testset, experts=True) if has_experts else net.score_calibration(testset)
+    rows = list(result[2].items()) if has_experts else []
+    rows.append(('fusion' if has_experts else 'model', result[:2]))
+    search = net.calibration_search(testset, temperatures) if temperatures is not None else None
+    if print_results:
+        for name, (m, _) in rows:
+            print('{:>15}: accuracy {:.3f} confidence {:.3f} ECE {:.4f} NLL {:.4f}'.format(
+                name, m['accuracy'], m['mean_confidence'], m['ECE'], m['NLL']))
+        if search is not None:
+            best = search['measures'][search['temperatures'].index(search['best'])]
+            print('best temperature {:g}: ECE {:.4f} NLL {:.4f}'.format(search['best'], best['ECE'], best['NLL']))
+    return result + (search,) if search is not None else result
+
+
 def evaluate_on_all_sequences(net, testset, sequence_of_image):
     """experiments/evaluation.py:42-55 (evaluate_on_all_synthia_seqs) on one pass instead of one evaluation per sequence:
     sequence_of_image names the sequence of every image of `testset`, in order.  Returns {sequence: measures}."""

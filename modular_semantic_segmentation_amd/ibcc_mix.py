@@ -67,6 +67,9 @@ class IbccFusion(BayesFusion):
     def _agreement_head(self):
         return None                 # score_agreement fuses the materialised maps through _fusion and ops.agreement_table
 
+    calibration_refusal = ('an IBCC fusion decides by a lookup over the experts\' label tuple; its posterior per tuple is not '
+                           'a per-pixel class score the calibration kernels take')
+
     def _lowres(self, batch):
         """(scores, biases, n, hi, wi) of the label-tuple heads; two experts share their paired launches as in every route."""
         if len(self.modalities) == 2:

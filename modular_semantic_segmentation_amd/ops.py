@@ -943,6 +943,164 @@ def agreement_table(labels, expert_labels, fused, num_classes, groups=None, num_
     return table
 
 
+# ---- calibration scoring (csrc/calibration.hip): reliability tables int64 [T, NB, 3] = (count, correct, sum of the confidence in
+# 2^-24 steps) per temperature and confidence bin, and the NLL sums float64 [T]; calibration.calibration_measures reads them
+
+def calibration_capacity(bin_bits, num_tables=1):
+    """Temperatures one calibration launch serves with `num_tables` tables per temperature (1: the fusion alone, 1 + E: the
+    experts' beside it); 0 outside the supported ranges.  No GPU call."""
+    return int(_lib.lib().xv_calibration_capacity(int(bin_bits), int(num_tables)))
+
+
+def _calibration_temperatures(temperatures, bin_bits):
+    """The temperatures as a list of floats and the bin count, checked here as the kernels check them."""
+    temps = [float(t) for t in np.atleast_1d(np.asarray(temperatures, np.float64))]
+    if not temps or not all(np.isfinite(t) and np.float32(t) > 0 and np.isfinite(np.float32(t)) for t in temps):
+        raise ValueError('temperatures must be finite and positive, at least one, got %r' % (temperatures,))
+    if not 4 <= int(bin_bits) <= 10:
+        raise ValueError('bin_bits must lie in 4..10, got %r' % (bin_bits,))
+    return temps, 1 << int(bin_bits)
+
+
+def _calibration_outputs(table, nll, name, groups, n, num_groups, lead, NT, NB, device):
+    """(table, nll, group ids): int64 [num_groups, *lead, NT, NB, 3] and float64 [num_groups, *lead, NT] (without the group axis
+    when there are no groups), zeroed ones made here when none are given."""
+    table, ids = _grouped_output(table, name, groups, n, num_groups, tuple(lead) + (NT, NB, 3), device)
+    shape = tuple(table.shape[:-2])
+    if nll is None:
+        nll = torch.zeros(shape, dtype=torch.float64, device=device)
+    _need(nll, torch.float64, name.replace('table', 'nll'))
+    if tuple(nll.shape) != shape:
+        raise ValueError('%s of shape %s, expected %s' % (name.replace('table', 'nll'), tuple(nll.shape), shape))
+    return table, nll, ids
+
+
+def _calibration_chunks(temps, cap, grouped, outs):
+    """Temperature chunks of at most `cap`: (c_float array, t0, t1, [(launch target, its final tensor or None)]).  A launch
+    writes its temperatures densely: without groups a slice of the temperature axis (the leading one of a table, the one behind
+    the experts of an expert table, which is then counted apart) is handed over; otherwise a zeroed stand-in that the caller
+    adds afterwards."""
+    NT = len(temps)
+    for t0 in range(0, NT, cap):
+        t1 = min(NT, t0 + cap)
+        targets = []
+        for out, taxis in outs:
+            if out is None:
+                targets.append((None, None))
+            elif (t0, t1) == (0, NT):
+                targets.append((out, None))
+            elif not grouped and taxis == 0:
+                targets.append((out[t0:t1], None))
+            else:
+                shape = list(out.shape)
+                shape[taxis + (1 if grouped else 0)] = t1 - t0
+                targets.append((torch.zeros(shape, dtype=out.dtype, device=out.device), out))
+        yield (ctypes.c_float * (t1 - t0))(*temps[t0:t1]), t0, t1, targets
+
+
+def _calibration_merge(targets, t0, t1, grouped, taxes):
+    for (part, out), taxis in zip(targets, taxes):
+        if out is not None:
+            axis = taxis + (1 if grouped else 0)
+            out.narrow(axis, t0, t1 - t0).add_(part)
+
+
+def calibration_table(values, labels, temperatures=1.0, bin_bits=10, kind=0, num_classes=None, groups=None, num_groups=1,
+                      table=None, nll=None):
+    """The reliability table of a MATERIALISED map: values float32 [n, ..., C], class scores in the log domain (kind 0) or
+    probabilities (kind 1: ln(1e-20 + p) after the winner is taken); labels int32 [n, ...].  Per temperature T and pixel with
+    0 <= label < C: conf = 1 / sum_k exp((s[k] - s[win]) / T), q = int(conf 2^24), bin = min(q >> (24 - bin_bits), NB - 1);
+    table[t][bin] += (1, win == label, q) and nll[t] += min(ln z - (s[label] - s[win]) / T, -ln 1e-10).  Accumulates into
+    table (int64 [T, NB, 3], [num_groups, T, NB, 3] with groups) and nll (float64 [T] / [num_groups, T]), made here, zeroed,
+    when None, and returns (table, nll).  More temperatures than one launch holds (calibration_capacity) go in several
+    launches.  `groups` as fused_head_joint_hist_grouped takes it; the image axis comes first."""
+    temps, NB = _calibration_temperatures(temperatures, bin_bits)
+    if kind not in (0, 1):
+        raise ValueError('kind must be 0 (scores) or 1 (probabilities), got %r' % (kind,))
+    _need(values, torch.float32, 'values')
+    _need(labels, torch.int32, 'labels')
+    C = int(values.shape[-1]) if num_classes is None else int(num_classes)
+    if not 2 <= C <= 32:
+        raise ValueError('the calibration table takes 2..32 classes, got %d' % C)
+    if labels.dim() < 2 or labels.numel() == 0 or tuple(values.shape) != tuple(labels.shape) + (C,):
+        raise ValueError('values of shape %s, labels of shape %s, %d classes: expected [n, ..., C] and non-empty [n, ...]'
+                         % (tuple(values.shape), tuple(labels.shape), C))
+    n = labels.shape[0]
+    table, nll, ids = _calibration_outputs(table, nll, 'table', groups, n, num_groups, (), len(temps), NB, values.device)
+    cap = calibration_capacity(bin_bits, 1)
+    for arr, t0, t1, targets in _calibration_chunks(temps, cap, groups is not None, [(table, 0), (nll, 0)]):
+        rc = _lib.lib().xv_calibration_table(_ptr(values), int(kind), _ptr(labels), _ptr(ids), n, labels.numel() // n, C,
+                                             ctypes.cast(arr, ctypes.c_void_p), t1 - t0, int(bin_bits), int(num_groups),
+                                             _ptr(targets[0][0]), _ptr(targets[1][0]), _stream())
+        _lib.check(rc, 'xv_calibration_table')
+        _calibration_merge(targets, t0, t1, groups is not None, (0, 0))
+    return table, nll
+
+
+def fused_head_multi_calibration(scores, biases, n, hi, wi, num_classes, mode, labels, temperatures=1.0, bin_bits=10, tab=None,
+                                 lognorm=None, logprior=None, groups=None, num_groups=1, table=None, nll=None, experts=False,
+                                 expert_table=None, expert_nll=None, max_workgroups=0):
+    """Two to four experts' low-resolution scores (as fused_head_multi takes them, with its tables for `mode`) -> the
+    reliability table of the FUSED posterior against labels (int32 [n, 8hi, 8wi]) in one launch, as calibration_table counts the
+    fused score map (Bayes, Dirichlet) or the mean probabilities (kind 1), without that map.  Returns (table, nll); with
+    experts=True (or expert_table / expert_nll given) also every expert's own table from its logits: (table, nll, expert_table
+    int64 [E, T, NB, 3], expert_nll float64 [E, T]), each with a leading group axis under `groups`.  All are accumulated into;
+    zeroed ones are made here when None.  More temperatures than one launch holds go in several launches on the same scores."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError('unknown fused head mode %r' % (mode,))
+    temps, NB = _calibration_temperatures(temperatures, bin_bits)
+    scores, biases = list(scores), list(biases)
+    if len(scores) != len(biases):
+        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
+    E, C = len(scores), int(num_classes)
+    if not 2 <= E <= 4:
+        raise ValueError('the calibration head takes two to four experts, got %d' % E)
+    cp = (C + 3) // 4 * 4
+    for i, (S, b) in enumerate(zip(scores, biases)):
+        _need(S, torch.float32, 'scores[%d]' % i)
+        _need(b, torch.float32, 'biases[%d]' % i)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+        if b.numel() != C:
+            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
+    _need(labels, torch.int32, 'labels')
+    if labels.numel() != n * hi * wi * 64:
+        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+    if mode == 2:
+        if tab is not None or lognorm is not None or logprior is not None:
+            raise ValueError('the mean takes no tables')
+    else:
+        if tab is None or logprior is None or (mode == 1 and lognorm is None):
+            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
+        if mode == 0 and lognorm is not None:
+            raise ValueError('Bayes fusion takes no lognorm')
+        for name, t, shape in (('tab', tab, (E, C, C)), ('lognorm', lognorm, (E, C)), ('logprior', logprior, (C,))):
+            if t is not None:
+                _need(t, torch.float32, name)
+                if tuple(t.shape) != shape:
+                    raise ValueError('%s of shape %s, expected %s' % (name, tuple(t.shape), shape))
+    device, NT, grouped = scores[0].device, len(temps), groups is not None
+    table, nll, ids = _calibration_outputs(table, nll, 'table', groups, n, num_groups, (), NT, NB, device)
+    experts = bool(experts) or expert_table is not None or expert_nll is not None
+    if experts:
+        expert_table, expert_nll, _ = _calibration_outputs(expert_table, expert_nll, 'expert_table', ids, n, num_groups, (E,),
+                                                           NT, NB, device)
+    cap = calibration_capacity(bin_bits, 1 + E if experts else 1)
+    if cap < 1:
+        raise ValueError('no calibration head for %d bin bits and %d experts' % (bin_bits, E))
+    S_arr, b_arr = _ptr_array(scores), _ptr_array(biases)
+    outs = [(table, 0), (nll, 0), (expert_table, 1), (expert_nll, 1)]
+    for arr, t0, t1, targets in _calibration_chunks(temps, cap, grouped, outs):
+        rc = _lib.lib().xv_fused_head_multi_calibration_fwd(
+            S_arr, b_arr, E, int(n), int(hi), int(wi), C, int(mode), _ptr(tab), _ptr(lognorm), _ptr(logprior), _ptr(labels),
+            _ptr(ids), int(num_groups), ctypes.cast(arr, ctypes.c_void_p), t1 - t0, int(bin_bits), _ptr(targets[0][0]),
+            _ptr(targets[1][0]), _ptr(targets[2][0]), _ptr(targets[3][0]), int(max_workgroups), _stream())
+        _lib.check(rc, 'xv_fused_head_multi_calibration_fwd')
+        _calibration_merge(targets, t0, t1, grouped, (0, 0, 1, 1))
+    return (table, nll, expert_table, expert_nll) if experts else (table, nll)
+
+
 # ---- label-tuple heads (csrc/tuple_lut.hip): the tuple of a pixel's expert labels is t = ((l_0 C + l_1) C + l_2) ..., expert
 # 0 most significant: the row-major index of a [C]*E decision array
 
