@@ -1,6 +1,8 @@
 """Parity of every HIP kernel (called through the C ABI) against the CPU oracle.
 Integer-valued operands make the conv checks bit-exact (fp32 sums of small integers are exact
-in any order), so a layout / swizzle / fragment-map bug cannot hide inside a tolerance."""
+in any order), so a layout / swizzle / fragment-map bug cannot hide inside a tolerance.
+Those sums stay below 256, where bf16 holds every integer: the store of these tests never rounds.  The rounding of the
+epilogues and of the weight packers is pinned, bit for bit, by tests/test_conv_rounding_gpu.py on wider integers."""
 import os
 
 import numpy as np
