@@ -33,14 +33,13 @@
 // four experts, 2.3 KB at 12 classes and three.  With the tables (Bayes [E][C][CM] + [CM]; Dirichlet [E][CM][CM] + [E][CM] +
 // [CM]: 16.6 KB at most) a workgroup holds under 29 KB, so the LDS never limits the residency the grid asks for.
 //
-// Work is dealt out as in multi_count.hip / grouped_score.hip: (image, part) slots, a workgroup counts ONE image at a time and
-// flushes into that image's group with one 64-bit global atomic per non-zero cell; part p of an image takes the steps p, p +
-// parts, ... of its pixels; the trip count is uniform over the workgroup (xv_wave_count needs whole waves; a lane past the end
-// recomputes the image's last pixel and counts nothing).  The grid is bounded, at most 512 workgroups (the rule for kernels
-// that end in atomics on few addresses, docs/HISTORY.md): two 512-thread workgroups per CU, the resident waves of the counting
-// head's four of 256.  group == nullptr: every image is group 0.  A group id is checked before anything is indexed with it.
+// Work is dealt out in (image, part) slots (xv_multi.h: xv_slot_plan); the trip count is uniform over the workgroup
+// (xv_wave_count needs whole waves; a lane past the end recomputes the image's last pixel and counts nothing).  The grid is
+// bounded, at most 512 workgroups: two 512-thread workgroups per CU, the resident waves of the counting head's four of 256.
+// group == nullptr: every image is group 0.  A group id is checked before anything is indexed with it.
 #include "xv_common.h"
 #include "xv_heads.h"  // the heads' per-pixel pieces and, through it, xv_fuse.h (sets `fp contract(on)` for what follows)
+#include "xv_multi.h"  // the host side: argument checks and the slot plan
 
 namespace {
 
@@ -238,60 +237,27 @@ __global__ __launch_bounds__(1024) void agreement_table_kernel(const int32_t* __
   }
 }
 
-// parts an image is cut into: as many as its steps of `per_part` pixels need, at most the image's share of the grid, at least one
-inline int agreement_parts(int64_t ppi, int per_part, int n, int bound) {
-  const int64_t need = (ppi + per_part - 1) / per_part;
-  const int64_t room = bound / n > 1 ? bound / n : 1;
-  return (int)(need < room ? need : room);
-}
-
 }  // namespace
 
 extern "C" int xv_fused_head_multi_agreement_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi,
                                                  int wi, int num_classes, int mode, const float* tab, const float* lognorm,
                                                  const float* logprior, const int32_t* labels, const int32_t* group,
                                                  int num_groups, int64_t* table, int max_workgroups, void* stream) {
-  XV_CHECK_ARG(S && bias && labels && table && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)table & 7) == 0);
-  XV_CHECK_ARG(((uintptr_t)group & 3) == 0);
-  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(mode >= 0 && mode <= 2 && n > 0 && hi > 0 && wi > 0 && max_workgroups >= 0);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
-  XV_CHECK_ARG(mode == 2 || (tab && logprior && ((uintptr_t)tab & 3) == 0 && ((uintptr_t)logprior & 3) == 0));
-  XV_CHECK_ARG(mode != 1 || (lognorm && ((uintptr_t)lognorm & 3) == 0));
+  XV_CHECK_ARG(labels && table && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)table & 7) == 0);
+  XV_CHECK_ARG(xv_mode_tables_ok(mode, tab, lognorm, logprior) && xv_group_ok(group, num_groups) && max_workgroups >= 0);
   HeadPtrs ptrs;
-  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
-    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
-    XV_CHECK_ARG(S[src] && bias[src] && ((uintptr_t)S[src] & 15) == 0 && ((uintptr_t)bias[src] & 3) == 0);  // 16-byte tap loads
-    ptrs.s[e] = S[src];
-    ptrs.b[e] = bias[src];
-  }
-  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  XV_CHECK_OK(xv_multi_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs));
   const int64_t ppi = (int64_t)hi * wi * 64;  // one image's pixels
   // two 512-thread workgroups per CU, never above 512, or the caller's bound
-  int bound = xv_num_cus() * 2;
-  if (bound > XV_AGREE_MAX_GRID) bound = XV_AGREE_MAX_GRID;
-  if (max_workgroups > 0 && max_workgroups < bound) bound = max_workgroups;
-  const int parts = agreement_parts(ppi, XV_AGREE_THREADS, n, bound);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's u32 counters)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
-  const size_t c = (size_t)num_classes, cm = (c + 3) / 4 * 4, e = (size_t)num_experts;
-  const size_t ntab = mode == 0 ? e * c * cm + cm : (mode == 1 ? e * cm * cm + e * cm + cm : 0);
-  const size_t lds = (ntab + (c << num_experts) * 6) * 4;
+  XvSlotPlan plan;
+  XV_CHECK_OK(xv_slot_plan(ppi, XV_AGREE_THREADS, ppi, n, xv_grid_bound(2, XV_AGREE_MAX_GRID, max_workgroups), plan));
+  const size_t lds = (xv_multi_table_floats(mode, num_experts, num_classes) + ((size_t)num_classes << num_experts) * 6) * 4;
   hipStream_t s = (hipStream_t)stream;
 #define XV_AG_MODE(CMV, MODE)                                                                                                \
-  hipLaunchKernelGGL((fused_head_multi_agreement_kernel<CMV, MODE>), dim3(grid), dim3(XV_AGREE_THREADS), lds, s, ptrs,        \
-                     num_experts, n, hi, wi, num_classes, tab, lognorm, logprior, labels, group, num_groups, parts,          \
+  hipLaunchKernelGGL((fused_head_multi_agreement_kernel<CMV, MODE>), dim3(plan.grid), dim3(XV_AGREE_THREADS), lds, s, ptrs,   \
+                     num_experts, n, hi, wi, num_classes, tab, lognorm, logprior, labels, group, num_groups, plan.parts,     \
                      reinterpret_cast<unsigned long long*>(table))
-#define XV_AG(CMV)          \
-  {                         \
-    if (mode == 0)          \
-      XV_AG_MODE(CMV, 0);   \
-    else if (mode == 1)     \
-      XV_AG_MODE(CMV, 1);   \
-    else                    \
-      XV_AG_MODE(CMV, 2);   \
-  }
+#define XV_AG(CMV) XV_MODE_SWITCH(mode, XV_AG_MODE, CMV)
   XV_CM_SWITCH(num_classes, XV_AG)
 #undef XV_AG
 #undef XV_AG_MODE
@@ -302,24 +268,16 @@ extern "C" int xv_agreement_table(const int32_t* labels, const int64_t* const* e
                                   const int64_t* fused, const int32_t* group, int n, int64_t ppi, int num_classes,
                                   int num_groups, int64_t* table, void* stream) {
   XV_CHECK_ARG(labels && expert_labels && fused && table && n >= 1 && ppi >= 1);
-  XV_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)group & 3) == 0 && ((uintptr_t)fused & 7) == 0 && ((uintptr_t)table & 7) == 0);
-  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
+  XV_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)fused & 7) == 0 && ((uintptr_t)table & 7) == 0);
+  XV_CHECK_ARG(xv_experts_classes_ok(num_experts, num_classes) && xv_group_ok(group, num_groups));
   AgreementMaps maps;
-  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
-    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
-    XV_CHECK_ARG(expert_labels[src] && ((uintptr_t)expert_labels[src] & 7) == 0);
-    maps.p[e] = expert_labels[src];
-  }
+  XV_CHECK_ARG(xv_fill_expert_slots(expert_labels, num_experts, 7, maps.p));
   XV_CHECK_SHAPE(ppi <= ((int64_t)1 << 40) / n);
   // one 16-wave workgroup per CU, never above 512, as xv_confusion_matrix_grouped
-  const int cus = xv_num_cus(), bound = cus < XV_AGREE_MAX_GRID ? cus : XV_AGREE_MAX_GRID;
-  const int parts = agreement_parts(ppi, 1024, n, bound);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's u32 counters)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
+  XvSlotPlan plan;
+  XV_CHECK_OK(xv_slot_plan(ppi, 1024, ppi, n, xv_grid_bound(1, XV_AGREE_MAX_GRID, 0), plan));
   const size_t lds = ((size_t)num_classes << num_experts) * 6 * 4;
-  hipLaunchKernelGGL(agreement_table_kernel, dim3(grid), dim3(1024), lds, (hipStream_t)stream, labels, maps, num_experts, fused,
-                     group, n, ppi, num_classes, num_groups, parts, reinterpret_cast<unsigned long long*>(table));
+  hipLaunchKernelGGL(agreement_table_kernel, dim3(plan.grid), dim3(1024), lds, (hipStream_t)stream, labels, maps, num_experts,
+                     fused, group, n, ppi, num_classes, num_groups, plan.parts, reinterpret_cast<unsigned long long*>(table));
   return xv_launch_status();
 }

@@ -27,13 +27,13 @@
 // fusion alone at ten bin bits, 1 with four experts' tables beside it.  A launch asks for what it uses, not for 160 KB.
 // THE TOP BIN is aggregated per wave before the LDS atomic (xv_calib.h: calib_wave_add says how).
 //
-// Work is dealt out as in agreement.hip: (image, part) slots, a workgroup counts ONE image at a time and flushes into that
-// image's group with one 64-bit global atomic per non-zero column of a non-empty bin; the trip count is uniform over the
-// workgroup; the grid is bounded, two 512-thread workgroups per CU and at most 512.  group == nullptr: every image is group 0.
-// A group id is checked before anything is indexed with it.
+// Work is dealt out in (image, part) slots (xv_multi.h: xv_slot_plan); a flush costs one 64-bit global atomic per non-zero
+// column of a non-empty bin; the trip count is uniform over the workgroup; the grid is bounded, two 512-thread workgroups per
+// CU and at most 512.  group == nullptr: every image is group 0.  A group id is checked before anything is indexed with it.
 #include "xv_common.h"
 #include "xv_heads.h"  // the heads' per-pixel pieces and, through it, xv_fuse.h (sets `fp contract(on)` for what follows)
 #include "xv_calib.h"
+#include "xv_multi.h"  // the host side: argument checks and the slot plan
 
 namespace {
 
@@ -289,13 +289,6 @@ __global__ __launch_bounds__(XV_CALIB_THREADS) void calibration_table_kernel(
   }
 }
 
-// parts an image is cut into: as many as its steps of `per_part` pixels need, at most the image's share of the grid, at least one
-inline int calib_parts(int64_t ppi, int per_part, int n, int bound) {
-  const int64_t need = (ppi + per_part - 1) / per_part;
-  const int64_t room = bound / n > 1 ? bound / n : 1;
-  return (int)(need < room ? need : room);
-}
-
 // bin bits, temperature count (against the capacity for `num_tables`) and every temperature finite and positive
 bool calib_args_ok(const float* temperatures, int num_temperatures, int bin_bits, int num_tables, CalibTemps& temps) {
   const int cap = calib_capacity(bin_bits, num_tables);
@@ -308,12 +301,10 @@ bool calib_args_ok(const float* temperatures, int num_temperatures, int bin_bits
   return true;
 }
 
-int calib_bound(int max_workgroups) {
-  // two 512-thread workgroups per CU, never above 512, or the caller's bound
-  int bound = xv_num_cus() * 2;
-  if (bound > XV_CALIB_MAX_GRID) bound = XV_CALIB_MAX_GRID;
-  if (max_workgroups > 0 && max_workgroups < bound) bound = max_workgroups;
-  return bound;
+// the slot plan of both forms: two 512-thread workgroups per CU, never above 512, or the caller's bound; the 32-bit counters
+// are a cell's count and correct halves
+int calib_plan(int64_t ppi, int n, int max_workgroups, XvSlotPlan& plan) {
+  return xv_slot_plan(ppi, XV_CALIB_THREADS, ppi, n, xv_grid_bound(2, XV_CALIB_MAX_GRID, max_workgroups), plan);
 }
 
 }  // namespace
@@ -324,18 +315,14 @@ extern "C" int xv_calibration_table(const float* values, int kind, const int32_t
                                     int64_t ppi, int num_classes, const float* temperatures, int num_temperatures, int bin_bits,
                                     int num_groups, int64_t* table, double* nll, void* stream) {
   XV_CHECK_ARG(values && labels && table && nll && n >= 1 && ppi >= 1 && (kind == 0 || kind == 1));
-  XV_CHECK_ARG(((uintptr_t)values & 3) == 0 && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)group & 3) == 0);
+  XV_CHECK_ARG(((uintptr_t)values & 3) == 0 && ((uintptr_t)labels & 3) == 0 && xv_group_ok(group, num_groups));
   XV_CHECK_ARG(((uintptr_t)table & 7) == 0 && ((uintptr_t)nll & 7) == 0);
   XV_CHECK_ARG(num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
   CalibTemps temps;
   XV_CHECK_ARG(calib_args_ok(temperatures, num_temperatures, bin_bits, 1, temps));
   XV_CHECK_SHAPE(ppi <= ((int64_t)1 << 40) / n);
-  const int bound = calib_bound(0);
-  const int parts = calib_parts(ppi, XV_CALIB_THREADS, n, bound);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's 32-bit count and correct halves)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
+  XvSlotPlan plan;
+  XV_CHECK_OK(calib_plan(ppi, n, 0, plan));
   const size_t lds = XV_CALIB_MAXT * 4 + (size_t)num_temperatures * ((16u << bin_bits) + XV_CALIB_NLL_COPIES * 8);
   const int vec = (num_classes & 3) == 0 && ((uintptr_t)values & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
@@ -345,8 +332,8 @@ extern "C" int xv_calibration_table(const float* values, int kind, const int32_t
     const hipError_t e =                                                                                                    \
         xv_allow_dynamic_lds(reinterpret_cast<const void*>(&calibration_table_kernel<CMV>), XV_CALIB_LDS, attr, false);     \
     if (e != hipSuccess) return (int)e;                                                                                     \
-    hipLaunchKernelGGL(calibration_table_kernel<CMV>, dim3(grid), dim3(XV_CALIB_THREADS), lds, s, values, kind, labels,     \
-                       group, n, ppi, num_classes, num_groups, parts, temps, num_temperatures, bin_bits, vec,               \
+    hipLaunchKernelGGL(calibration_table_kernel<CMV>, dim3(plan.grid), dim3(XV_CALIB_THREADS), lds, s, values, kind, labels, \
+                       group, n, ppi, num_classes, num_groups, plan.parts, temps, num_temperatures, bin_bits, vec,          \
                        reinterpret_cast<unsigned long long*>(table), nll);                                                  \
   }
   XV_CM_SWITCH(num_classes, XV_CT)
@@ -360,35 +347,19 @@ extern "C" int xv_fused_head_multi_calibration_fwd(const float* const* S, const 
                                                    int num_groups, const float* temperatures, int num_temperatures, int bin_bits,
                                                    int64_t* table, double* nll, int64_t* expert_table, double* expert_nll,
                                                    int max_workgroups, void* stream) {
-  XV_CHECK_ARG(S && bias && labels && table && nll && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)table & 7) == 0);
-  XV_CHECK_ARG(((uintptr_t)group & 3) == 0 && ((uintptr_t)nll & 7) == 0);
+  XV_CHECK_ARG(labels && table && nll && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)table & 7) == 0 && ((uintptr_t)nll & 7) == 0);
   XV_CHECK_ARG((expert_table == nullptr) == (expert_nll == nullptr));
   XV_CHECK_ARG(((uintptr_t)expert_table & 7) == 0 && ((uintptr_t)expert_nll & 7) == 0);
-  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(mode >= 0 && mode <= 2 && n > 0 && hi > 0 && wi > 0 && max_workgroups >= 0);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
-  XV_CHECK_ARG(mode == 2 || (tab && logprior && ((uintptr_t)tab & 3) == 0 && ((uintptr_t)logprior & 3) == 0));
-  XV_CHECK_ARG(mode != 1 || (lognorm && ((uintptr_t)lognorm & 3) == 0));
+  XV_CHECK_ARG(xv_mode_tables_ok(mode, tab, lognorm, logprior) && xv_group_ok(group, num_groups) && max_workgroups >= 0);
+  XV_CHECK_ARG(xv_experts_classes_ok(num_experts, num_classes));  // (before the capacity is asked for 1 + num_experts tables)
   const int ntables = expert_table != nullptr ? 1 + num_experts : 1;
   CalibTemps temps;
   XV_CHECK_ARG(calib_args_ok(temperatures, num_temperatures, bin_bits, ntables, temps));
   HeadPtrs ptrs;
-  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
-    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
-    XV_CHECK_ARG(S[src] && bias[src] && ((uintptr_t)S[src] & 15) == 0 && ((uintptr_t)bias[src] & 3) == 0);  // 16-byte tap loads
-    ptrs.s[e] = S[src];
-    ptrs.b[e] = bias[src];
-  }
-  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
-  const int64_t ppi = (int64_t)hi * wi * 64;  // one image's pixels
-  const int bound = calib_bound(max_workgroups);
-  const int parts = calib_parts(ppi, XV_CALIB_THREADS, n, bound);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's 32-bit count and correct halves)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
-  const size_t c = (size_t)num_classes, cm = (c + 3) / 4 * 4, e = (size_t)num_experts;
-  const size_t ntab = mode == 0 ? e * c * cm + cm : (mode == 1 ? e * cm * cm + e * cm + cm : 0);
-  const size_t lds = (ntab + XV_CALIB_MAXT + 3) / 4 * 16 +
+  XV_CHECK_OK(xv_multi_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs));
+  XvSlotPlan plan;
+  XV_CHECK_OK(calib_plan((int64_t)hi * wi * 64, n, max_workgroups, plan));  // (one image's pixels)
+  const size_t lds = (xv_multi_table_floats(mode, num_experts, num_classes) + XV_CALIB_MAXT + 3) / 4 * 16 +
                      (size_t)ntables * num_temperatures * ((16u << bin_bits) + XV_CALIB_NLL_COPIES * 8);
   hipStream_t s = (hipStream_t)stream;
 #define XV_CF_MODE(CMV, MODE)                                                                                               \
@@ -397,20 +368,12 @@ extern "C" int xv_fused_head_multi_calibration_fwd(const float* const* S, const 
     const hipError_t err = xv_allow_dynamic_lds(                                                                            \
         reinterpret_cast<const void*>(&fused_head_multi_calibration_kernel<CMV, MODE>), XV_CALIB_LDS, attr, false);         \
     if (err != hipSuccess) return (int)err;                                                                                 \
-    hipLaunchKernelGGL((fused_head_multi_calibration_kernel<CMV, MODE>), dim3(grid), dim3(XV_CALIB_THREADS), lds, s, ptrs,  \
-                       num_experts, n, hi, wi, num_classes, tab, lognorm, logprior, labels, group, num_groups, parts, temps, \
-                       num_temperatures, bin_bits, ntables, reinterpret_cast<unsigned long long*>(table), nll,              \
-                       reinterpret_cast<unsigned long long*>(expert_table), expert_nll);                                    \
+    hipLaunchKernelGGL((fused_head_multi_calibration_kernel<CMV, MODE>), dim3(plan.grid), dim3(XV_CALIB_THREADS), lds, s,   \
+                       ptrs, num_experts, n, hi, wi, num_classes, tab, lognorm, logprior, labels, group, num_groups,        \
+                       plan.parts, temps, num_temperatures, bin_bits, ntables, reinterpret_cast<unsigned long long*>(table), \
+                       nll, reinterpret_cast<unsigned long long*>(expert_table), expert_nll);                               \
   }
-#define XV_CF(CMV)          \
-  {                         \
-    if (mode == 0)          \
-      XV_CF_MODE(CMV, 0)    \
-    else if (mode == 1)     \
-      XV_CF_MODE(CMV, 1)    \
-    else                    \
-      XV_CF_MODE(CMV, 2)    \
-  }
+#define XV_CF(CMV) XV_MODE_SWITCH(mode, XV_CF_MODE, CMV)
   XV_CM_SWITCH(num_classes, XV_CF)
 #undef XV_CF
 #undef XV_CF_MODE

@@ -3,14 +3,12 @@
 // (experiments/evaluation.py:42-55 scores a network once per sequence; a paired bootstrap needs a matrix per image).
 //   xv_confusion_matrix_grouped           cm[group[i]][label][pred] += 1            (xv_confusion_matrix per group)
 //   xv_fused_head_joint_hist_grouped_fwd  hist[group[i]][label][a][b] += 1          (xv_fused_head_joint_hist_fwd per group)
-// Both deal out (image, part) slots to workgroups: a workgroup counts the pixels of ONE image at a time into counters in its
-// LDS and flushes them into that image's group with one 64-bit global atomic per non-zero cell.  The grid is bounded (a kernel
-// that ends in atomics on few addresses runs a bounded grid, docs/HISTORY.md); while images x parts fit the bound -- every batch
-// size the models run -- a workgroup has exactly one slot and flushes once, beyond it a workgroup walks its slots one after the
-// other.  The group ids are read from device memory and checked before anything is indexed with them: an id outside [0, G)
-// counts nothing.
+// Both deal out (image, part) slots to workgroups (xv_multi.h: xv_slot_plan, with the bounded grid); while images x parts fit
+// the bound -- every batch size the models run -- a workgroup has exactly one slot and flushes once.  The group ids are read
+// from device memory and checked before anything is indexed with them: an id outside [0, G) counts nothing.
 #include "xv_common.h"
 #include "xv_heads.h"  // the heads' per-pixel pieces (sets `fp contract(on)` for what follows, as heads.hip has it)
+#include "xv_multi.h"  // the host side: the grid bound and the slot plan
 
 namespace {
 
@@ -19,14 +17,6 @@ inline int grouped_table_copies(size_t cells) {
   int rep = 32;
   while (rep > 1 && cells * rep * 4 > 64 * 1024) rep >>= 1;
   return rep;
-}
-
-// parts an image is cut into: as many as its `items` (work items of `per_part` per step) need, at most the image's share of
-// `bound` workgroups, at least one
-inline int grouped_parts(int64_t items, int per_part, int n, int bound) {
-  const int64_t need = (items + per_part - 1) / per_part;
-  const int64_t room = bound / n > 1 ? bound / n : 1;
-  return (int)(need < room ? need : room);
 }
 
 // base_model.py:136-151 per group.  confusion_kernel's counting: `XV_REP` u32 copies of the [C][C] table in LDS, copy = lane &
@@ -162,13 +152,10 @@ extern "C" int xv_confusion_matrix_grouped(const int32_t* labels, const int64_t*
   // every image starts 16-byte aligned in both maps: whole label quads per image
   const int vec = ((uintptr_t)labels & 15) == 0 && ((uintptr_t)pred & 15) == 0 && (ppi & 3) == 0;
   // one 16-wave workgroup per CU, as xv_confusion_matrix; at most the 512 of the rule for kernels that end in such atomics
-  const int cus = xv_num_cus(), bound = cus < 512 ? cus : 512;
-  const int parts = grouped_parts((ppi + 3) / 4, 1024, n, bound);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's u32 counters)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
-  hipLaunchKernelGGL(confusion_grouped_kernel, dim3(grid), dim3(1024), lds, (hipStream_t)stream, labels, pred, group, n, ppi,
-                     num_classes, num_groups, parts, reinterpret_cast<unsigned long long*>(cm), rep, vec);
+  XvSlotPlan plan;  // (a thread takes four pixels a step)
+  XV_CHECK_OK(xv_slot_plan((ppi + 3) / 4, 1024, ppi, n, xv_grid_bound(1, 512, 0), plan));
+  hipLaunchKernelGGL(confusion_grouped_kernel, dim3(plan.grid), dim3(1024), lds, (hipStream_t)stream, labels, pred, group, n,
+                     ppi, num_classes, num_groups, plan.parts, reinterpret_cast<unsigned long long*>(cm), rep, vec);
   return xv_launch_status();
 }
 
@@ -182,17 +169,13 @@ extern "C" int xv_fused_head_joint_hist_grouped_fwd(const float* Sa, const float
   XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
   const int64_t nquads = (int64_t)hi * wi * 64 / xv_joint_hist_pixels((num_classes + 3) / 4 * 4);  // one image's pixel groups
   // four 256-thread workgroups per CU as the ungrouped head, or the caller's bound
-  int bound = xv_num_cus() * 4;
-  if (max_workgroups > 0 && max_workgroups < bound) bound = max_workgroups;
-  const int parts = grouped_parts(nquads, 256, n, bound);
-  XV_CHECK_SHAPE(nquads / parts < ((int64_t)1 << 29));  // (a workgroup's u32 counters, four pixels per group)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
+  XvSlotPlan plan;  // (a pixel group adds at most four to a counter)
+  XV_CHECK_OK(xv_slot_plan(nquads, 256, nquads * 4, n, xv_grid_bound(4, 0, max_workgroups), plan));
   const size_t lds = (size_t)num_classes * num_classes * num_classes * 4;
   hipStream_t s = (hipStream_t)stream;
 #define XV_GJH(CMV)                                                                                                          \
-  hipLaunchKernelGGL(fused_head_joint_hist_grouped_kernel<CMV>, dim3(grid), dim3(256), lds, s, Sa, Sb, bias_a, bias_b, n, hi, \
-                     wi, num_classes, labels, group, num_groups, parts, reinterpret_cast<unsigned long long*>(hist))
+  hipLaunchKernelGGL(fused_head_joint_hist_grouped_kernel<CMV>, dim3(plan.grid), dim3(256), lds, s, Sa, Sb, bias_a, bias_b, n, \
+                     hi, wi, num_classes, labels, group, num_groups, plan.parts, reinterpret_cast<unsigned long long*>(hist))
   switch ((num_classes + 3) / 4) {  // (XV_CM_SWITCH up to the 20 classes this entry point takes: nothing is built beyond)
     case 1: XV_GJH(4); break;
     case 2: XV_GJH(8); break;

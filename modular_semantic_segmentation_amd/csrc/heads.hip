@@ -4,6 +4,7 @@
 
 #include "xv_common.h"
 #include "xv_heads.h"
+#include "xv_multi.h"  // the host side of the multi-expert head: argument checks, the grid bound
 
 // Floating-point contraction by the SOURCE only (a * b + c inside one expression), never across statements: the fused heads
 // and the unfused path (decoder head -> probability maps -> fusion kernel) must produce the same bits; see xv_fuse.h.
@@ -1575,8 +1576,7 @@ extern "C" int xv_fused_head_grid_capacity(int num_classes) {
 
 // workgroups of a grid-stride launch over `items` (256 per workgroup and step): four per CU, or the caller's bound
 static int grid_score_workgroups(int64_t items, int max_workgroups) {
-  const int grid = xv_grid_for(items, 256, xv_num_cus() * 4);
-  return max_workgroups > 0 && max_workgroups < grid ? max_workgroups : grid;
+  return xv_grid_for(items, 256, xv_grid_bound(4, 0, max_workgroups));
 }
 
 extern "C" int xv_fused_head_grid_score_fwd(const float* Sa, const float* Sb, const float* bias_a, const float* bias_b, int n,
@@ -1676,47 +1676,28 @@ extern "C" int xv_fused_head_average_count_fwd(const float* Sa, const float* Sb,
 extern "C" int xv_fused_head_multi_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
                                        int num_classes, int mode, const float* tab, const float* lognorm,
                                        const float* logprior, int64_t* fused_label, void* stream) {
-  XV_CHECK_ARG(S && bias && fused_label && ((uintptr_t)fused_label & 15) == 0);
-  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(mode >= 0 && mode <= 2 && n > 0 && hi > 0 && wi > 0);
-  XV_CHECK_ARG(mode == 2 || (tab && logprior && ((uintptr_t)tab & 3) == 0 && ((uintptr_t)logprior & 3) == 0));
-  XV_CHECK_ARG(mode != 1 || (lognorm && ((uintptr_t)lognorm & 3) == 0));
+  XV_CHECK_ARG(fused_label && ((uintptr_t)fused_label & 15) == 0 && xv_mode_tables_ok(mode, tab, lognorm, logprior));
   HeadPtrs ptrs;
-  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
-    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
-    XV_CHECK_ARG(S[src] && bias[src] && ((uintptr_t)S[src] & 15) == 0 && ((uintptr_t)bias[src] & 3) == 0);  // 16-byte tap loads
-    ptrs.s[e] = S[src];
-    ptrs.b[e] = bias[src];
-  }
-  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  XV_CHECK_OK(xv_multi_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs));
   const int64_t nquads = (int64_t)n * hi * wi * 64 / xv_multi_pixels(mode);  // (8 wi is a multiple of every pixel group)
   XV_CHECK_SHAPE((nquads + 255) / 256 <= 0x7fffffff);
   const unsigned grid = (unsigned)((nquads + 255) / 256);
   const int ndec = mode == 0 ? multi_head_dec_entries(num_classes, num_experts) : 0;
   hipStream_t s = (hipStream_t)stream;
-#define XV_FM_MODE(CMV, MODE, FULL)                                                                                        \
+  // (this kernel keeps the lognorm slot [E][CM] in Bayes mode too, E CM floats more than xv_multi_table_floats; then dec)
+  const size_t cm = ((size_t)num_classes + 3) / 4 * 4;
+  const size_t lds = mode == 2 ? 0
+                               : (num_experts * (mode == 1 ? cm : (size_t)num_classes) * cm + (num_experts + 1) * cm) * 4 +
+                                     (size_t)(ndec + 15) / 16 * 16;
+#define XV_FM_MODE(CMV, FULL, MODE)                                                                                        \
   hipLaunchKernelGGL((fused_head_multi_kernel<CMV, MODE, FULL>), dim3(grid), dim3(256), lds, s, ptrs, num_experts, n, hi, wi, \
                      num_classes, ndec, tab, lognorm, logprior, fused_label)
-#define XV_FM(CMV)                                                                                                      \
-  {                                                                                                                     \
-    const size_t lds = mode == 2 ? 0                                                                                    \
-                                 : (size_t)(num_experts * (mode == 1 ? CMV : num_classes) * CMV + (num_experts + 1) * CMV) * 4 + \
-                                       (size_t)(ndec + 15) / 16 * 16;                                                   \
-    if (num_classes == CMV) {                                                                                           \
-      if (mode == 0)                                                                                                    \
-        XV_FM_MODE(CMV, 0, true);                                                                                       \
-      else if (mode == 1)                                                                                               \
-        XV_FM_MODE(CMV, 1, true);                                                                                       \
-      else                                                                                                              \
-        XV_FM_MODE(CMV, 2, true);                                                                                       \
-    } else {                                                                                                            \
-      if (mode == 0)                                                                                                    \
-        XV_FM_MODE(CMV, 0, false);                                                                                      \
-      else if (mode == 1)                                                                                               \
-        XV_FM_MODE(CMV, 1, false);                                                                                      \
-      else                                                                                                              \
-        XV_FM_MODE(CMV, 2, false);                                                                                      \
-    }                                                                                                                   \
+#define XV_FM(CMV)                                 \
+  {                                                \
+    if (num_classes == CMV)                        \
+      XV_MODE_SWITCH(mode, XV_FM_MODE, CMV, true)  \
+    else                                           \
+      XV_MODE_SWITCH(mode, XV_FM_MODE, CMV, false) \
   }
   XV_CM_SWITCH(num_classes, XV_FM)
 #undef XV_FM

@@ -25,12 +25,10 @@
 // log-probabilities, which a rolled loop would have to index by a run-time expert number: it is instantiated per expert
 // count, EU = 2, 3, 4, and unrolled.
 //
-// Work is dealt out as in grouped_score.hip: (image, part) slots, a workgroup counts ONE image at a time into u32 counters in
-// its LDS through xv_wave_count and flushes them into that image's group with one 64-bit global atomic per non-zero cell; part
-// p of an image takes the steps p, p + parts, ... of its pixels, the trip count is uniform over the workgroup (xv_wave_count
-// needs whole waves; a lane past the end recomputes the image's last pixel and counts nothing).  The grid is bounded (four
-// workgroups per CU, or the caller's bound); while images x parts fit it a workgroup has one slot and flushes once.  group ==
-// nullptr: every image is group 0.  A group id is checked before anything is indexed with it: outside [0, NG) counts nothing.
+// Work is dealt out in (image, part) slots (xv_multi.h: xv_slot_plan), counted through xv_wave_count; the trip count is
+// uniform over the workgroup (xv_wave_count needs whole waves; a lane past the end recomputes the image's last pixel and counts
+// nothing).  The grid is bounded (four workgroups per CU, or the caller's bound).  group == nullptr: every image is group 0.
+// A group id is checked before anything is indexed with it: outside [0, NG) counts nothing.
 //
 // LDS of one launch, 40 KB at most (four workgroups per CU, as the grid-scoring heads of heads.hip), in this order:
 //   MODE 0   tab [E][C][CM], logprior [G][CM]
@@ -42,6 +40,7 @@
 
 #include "xv_common.h"
 #include "xv_heads.h"  // the heads' per-pixel pieces (sets `fp contract(on)` for what follows, as heads.hip has it)
+#include "xv_multi.h"  // the host side: argument checks and the slot plan
 
 namespace {
 
@@ -324,38 +323,22 @@ extern "C" int xv_fused_head_multi_count_fwd(const float* const* S, const float*
                                              const float* lognorm, const float* logprior, const int32_t* labels,
                                              const int32_t* group, int num_groups, int64_t* cm, int64_t* expert_cm,
                                              int max_workgroups, void* stream) {
-  XV_CHECK_ARG(S && bias && labels && cm && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)cm & 7) == 0);
-  XV_CHECK_ARG(((uintptr_t)expert_cm & 7) == 0 && ((uintptr_t)group & 3) == 0);
-  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(mode >= 0 && mode <= 2 && n > 0 && hi > 0 && wi > 0 && max_workgroups >= 0);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
+  XV_CHECK_ARG(labels && cm && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)cm & 7) == 0 && ((uintptr_t)expert_cm & 7) == 0);
+  XV_CHECK_ARG(xv_mode_tables_ok(mode, tab, lognorm, logprior) && xv_group_ok(group, num_groups) && max_workgroups >= 0);
   XV_CHECK_ARG(num_points >= 1 && num_points <= xv_fused_head_multi_count_capacity(num_classes, num_experts, mode));
-  XV_CHECK_ARG(mode == 2 || (tab && logprior && ((uintptr_t)tab & 3) == 0 && ((uintptr_t)logprior & 3) == 0));
-  XV_CHECK_ARG(mode != 1 || (lognorm && ((uintptr_t)lognorm & 3) == 0));
   HeadPtrs ptrs;
-  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
-    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
-    XV_CHECK_ARG(S[src] && bias[src] && ((uintptr_t)S[src] & 15) == 0 && ((uintptr_t)bias[src] & 3) == 0);  // 16-byte tap loads
-    ptrs.s[e] = S[src];
-    ptrs.b[e] = bias[src];
-  }
-  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
+  XV_CHECK_OK(xv_multi_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs));
   const int64_t ppi = (int64_t)hi * wi * 64;  // one image's pixels
   // four 256-thread workgroups per CU as the two-expert counting heads, or the caller's bound
-  int bound = xv_num_cus() * 4;
-  if (max_workgroups > 0 && max_workgroups < bound) bound = max_workgroups;
-  const int64_t need = (ppi + 255) / 256, room = bound / n > 1 ? bound / n : 1;
-  const int parts = (int)(need < room ? need : room);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's u32 counters)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
+  XvSlotPlan plan;
+  XV_CHECK_OK(xv_slot_plan(ppi, 256, ppi, n, xv_grid_bound(4, 0, max_workgroups), plan));
   const size_t lds = multi_count_point_bytes(num_classes, num_experts, mode) * num_points +
                      multi_count_fixed_bytes(num_classes, num_experts, mode) -
                      (expert_cm ? 0 : (size_t)num_experts * num_classes * num_classes * 4);
   hipStream_t s = (hipStream_t)stream;
 #define XV_MC_MODE(CMV, MODE, EU)                                                                                            \
-  hipLaunchKernelGGL((fused_head_multi_count_kernel<CMV, MODE, EU>), dim3(grid), dim3(256), lds, s, ptrs, num_experts, n, hi, \
-                     wi, num_classes, num_points, tab, lognorm, logprior, labels, group, num_groups, parts,                 \
+  hipLaunchKernelGGL((fused_head_multi_count_kernel<CMV, MODE, EU>), dim3(plan.grid), dim3(256), lds, s, ptrs, num_experts, \
+                     n, hi, wi, num_classes, num_points, tab, lognorm, logprior, labels, group, num_groups, plan.parts,     \
                      reinterpret_cast<unsigned long long*>(cm), reinterpret_cast<unsigned long long*>(expert_cm))
 #define XV_MC(CMV)                  \
   {                                 \

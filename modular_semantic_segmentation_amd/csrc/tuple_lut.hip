@@ -12,13 +12,10 @@
 //   xv_fused_head_multi_lut_fwd          fused_label = lut[t]: four pixels per thread, two 16-byte stores, as the Bayes head
 //   xv_fused_head_multi_lut_count_fwd    cm[group][label][lut[t]] += 1 over the pixels with 0 <= label < C; no label map
 //
-// The two counting kernels deal their work out as agreement.hip / multi_count.hip: (image, part) slots, a workgroup counts ONE
-// image at a time into u32 counters in its LDS through xv_wave_count and flushes them into that image's group with one 64-bit
-// global atomic per non-zero cell, so a counter never wraps; part p of an image takes the steps p, p + parts, ... of its
-// pixels, the trip count is uniform over the workgroup (xv_wave_count needs whole waves; a lane past the end recomputes the
-// image's last pixel and counts nothing).  The grid is bounded, at most 512 workgroups of 512 threads (the rule for kernels
-// that end in atomics on few addresses).  group == nullptr: every image is group 0.  A group id is checked before anything
-// is indexed with it.
+// The two counting kernels deal their work out in (image, part) slots (xv_multi.h: xv_slot_plan), counted through
+// xv_wave_count, so a counter never wraps; the trip count is uniform over the workgroup (xv_wave_count needs whole waves; a
+// lane past the end recomputes the image's last pixel and counts nothing).  The grid is bounded, at most 512 workgroups of
+// 512 threads.  group == nullptr: every image is group 0.  A group id is checked before anything is indexed with it.
 //
 // LDS.  The histogram holds T u32 counters and nothing else; the counting lookup holds the table (T bytes, rounded up to 16)
 // and C C u32 counters; the lookup head holds the table.  The histogram is the largest, so it sets what is served: 4 T bytes
@@ -27,6 +24,7 @@
 // workgroup is two waves per SIMD, which is what these kernels are held to.
 #include "xv_common.h"
 #include "xv_heads.h"  // the heads' per-pixel pieces (sets `fp contract(on)` for what follows, as heads.hip has it)
+#include "xv_multi.h"  // the host side: argument checks and the slot plan
 
 namespace {
 
@@ -185,17 +183,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xv_lut_wave
 // the checks the three entry points share; on success ptrs holds the experts' pointers
 int tuple_check_experts(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
                         int num_classes, HeadPtrs& ptrs) {
-  XV_CHECK_ARG(S && bias);
-  XV_CHECK_ARG(num_experts >= 2 && num_experts <= XV_MULTI_MAXE && num_classes >= 2 && num_classes <= 32);
-  XV_CHECK_ARG(n > 0 && hi > 0 && wi > 0);
-  for (int e = 0; e < XV_MULTI_MAXE; ++e) {
-    const int src = e < num_experts ? e : 0;  // (unused slots repeat expert 0: never read, never null)
-    XV_CHECK_ARG(S[src] && bias[src] && ((uintptr_t)S[src] & 15) == 0 && ((uintptr_t)bias[src] & 3) == 0);  // 16-byte tap loads
-    ptrs.s[e] = S[src];
-    ptrs.b[e] = bias[src];
-  }
+  XV_CHECK_OK(xv_multi_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs));
   XV_CHECK_SHAPE(tuple_count(num_classes, num_experts) > 0);
-  XV_CHECK_SHAPE(xv_dims_sane(n, hi, wi));
   return XV_OK;
 }
 
@@ -207,14 +196,8 @@ int tuple_launch(const HeadPtrs& ptrs, int num_experts, int n, int hi, int wi, i
   const int T = (int)tuple_count(num_classes, num_experts);
   const int64_t ppi = (int64_t)hi * wi * 64;  // one image's pixels
   // two 512-thread workgroups per CU where the LDS lets them, never above 512, or the caller's bound
-  int bound = xv_num_cus() * 2;
-  if (bound > XV_TUPLE_MAX_GRID) bound = XV_TUPLE_MAX_GRID;
-  if (max_workgroups > 0 && max_workgroups < bound) bound = max_workgroups;
-  const int64_t need = (ppi + XV_TUPLE_THREADS - 1) / XV_TUPLE_THREADS, room = bound / n > 1 ? bound / n : 1;
-  const int parts = (int)(need < room ? need : room);
-  XV_CHECK_SHAPE(ppi / parts < ((int64_t)1 << 31));  // (a workgroup's u32 counters)
-  const int64_t slots = (int64_t)n * parts;
-  const int grid = (int)(slots < bound ? slots : bound);
+  XvSlotPlan plan;
+  XV_CHECK_OK(xv_slot_plan(ppi, XV_TUPLE_THREADS, ppi, n, xv_grid_bound(2, XV_TUPLE_MAX_GRID, max_workgroups), plan));
   const size_t lds = COUNT ? (size_t)(T + 15) / 16 * 16 + (size_t)num_classes * num_classes * 4 : (size_t)T * 4;
 #define XV_TL(CMV)                                                                                                         \
   {                                                                                                                        \
@@ -222,8 +205,8 @@ int tuple_launch(const HeadPtrs& ptrs, int num_experts, int n, int hi, int wi, i
     const hipError_t e = xv_allow_dynamic_lds(reinterpret_cast<const void*>(&fused_head_multi_tuple_kernel<CMV, COUNT>),   \
                                               XV_TUPLE_LDS, attr, false);                                                  \
     if (e != hipSuccess) return (int)e;                                                                                    \
-    hipLaunchKernelGGL((fused_head_multi_tuple_kernel<CMV, COUNT>), dim3(grid), dim3(XV_TUPLE_THREADS), lds, s, ptrs,       \
-                       num_experts, n, hi, wi, num_classes, T, lut, labels, group, num_groups, parts,                      \
+    hipLaunchKernelGGL((fused_head_multi_tuple_kernel<CMV, COUNT>), dim3(plan.grid), dim3(XV_TUPLE_THREADS), lds, s, ptrs,  \
+                       num_experts, n, hi, wi, num_classes, T, lut, labels, group, num_groups, plan.parts,                 \
                        reinterpret_cast<unsigned long long*>(out));                                                        \
   }
   XV_CM_SWITCH(num_classes, XV_TL)
@@ -240,8 +223,7 @@ extern "C" int xv_tuple_capacity(int num_classes, int num_experts) {
 extern "C" int xv_fused_head_multi_tuple_hist_fwd(const float* const* S, const float* const* bias, int num_experts, int n,
                                                   int hi, int wi, int num_classes, const int32_t* group, int num_groups,
                                                   int64_t* hist, int max_workgroups, void* stream) {
-  XV_CHECK_ARG(hist && ((uintptr_t)hist & 7) == 0 && ((uintptr_t)group & 3) == 0 && max_workgroups >= 0);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
+  XV_CHECK_ARG(hist && ((uintptr_t)hist & 7) == 0 && xv_group_ok(group, num_groups) && max_workgroups >= 0);
   HeadPtrs ptrs;
   const int rc = tuple_check_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs);
   if (rc != XV_OK) return rc;
@@ -254,8 +236,7 @@ extern "C" int xv_fused_head_multi_lut_count_fwd(const float* const* S, const fl
                                                  const int32_t* group, int num_groups, int64_t* cm, int max_workgroups,
                                                  void* stream) {
   XV_CHECK_ARG(lut && labels && cm && ((uintptr_t)lut & 3) == 0 && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)cm & 7) == 0);
-  XV_CHECK_ARG(((uintptr_t)group & 3) == 0 && max_workgroups >= 0);
-  XV_CHECK_ARG(num_groups >= 1 && (group != nullptr || num_groups == 1));
+  XV_CHECK_ARG(xv_group_ok(group, num_groups) && max_workgroups >= 0);
   HeadPtrs ptrs;
   const int rc = tuple_check_experts(S, bias, num_experts, n, hi, wi, num_classes, ptrs);
   if (rc != XV_OK) return rc;

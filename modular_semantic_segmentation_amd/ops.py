@@ -609,9 +609,76 @@ def _check_lowres_pair(Sa, Sb, n, hi, wi, num_classes, labels):
         _need(S, torch.float32, name)
         if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
             raise ValueError('low-resolution scores %s of shape %s, expected %s' % (name, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+    _check_labels(labels, n, hi, wi)
+
+
+def _check_labels(labels, n, hi, wi):
+    """The ground truth of a counting head: int32, one label per output pixel."""
     _need(labels, torch.int32, 'labels')
     if labels.numel() != n * hi * wi * 64:
         raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+
+
+def _label_output(out, n, hi, wi, device):
+    """The label map a head writes, int64 [n, 8hi, 8wi]: made here when None, else checked."""
+    if out is None:
+        return torch.empty((n, 8 * hi, 8 * wi), dtype=torch.int64, device=device)
+    if out.dtype != torch.int64 or out.numel() != n * hi * wi * 64:
+        raise ValueError('out must be int64 of %d elements' % (n * hi * wi * 64))
+    return out
+
+
+# ---- what the heads over two to four experts' low-resolution scores check before they launch (fused_head_multi and its six
+# siblings).  Which layer refuses what differs between the siblings ON PURPOSE and is pinned by
+# tests/test_multi_expert_python_refusals_gpu.py: fused_head_multi leaves the expert count, the mode and missing tables to the
+# native check (XvError, XV_EINVAL); the counting form leaves the expert count to its capacity query; the others refuse here.
+
+def _check_experts(scores, biases, n, hi, wi, num_classes, what=None):
+    """(scores, biases, E, C): lists of equal length, every score a float32 CUDA tensor [n, hi+2, wi+2, CP], every bias of C
+    values.  `what` names a head that refuses anything but two to four experts here; None leaves the count to the caller."""
+    scores, biases = list(scores), list(biases)
+    if len(scores) != len(biases):
+        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
+    E, C = len(scores), int(num_classes)
+    if what is not None and not 2 <= E <= 4:
+        raise ValueError('%s takes two to four experts, got %d' % (what, E))
+    cp = (C + 3) // 4 * 4
+    for i, (S, b) in enumerate(zip(scores, biases)):
+        _need(S, torch.float32, 'scores[%d]' % i)
+        _need(b, torch.float32, 'biases[%d]' % i)
+        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
+            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
+        if b.numel() != C:
+            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
+    return scores, biases, E, C
+
+
+def _check_fusion_tables(mode, E, C, tab, lognorm, logprior, required=True, per_point=False):
+    """The fusion tables of a multi-expert head for `mode`: Bayes tab [E,C,C] and logprior [C]; Dirichlet tab [E,C,C], lognorm
+    [E,C] and logprior [C]; the mean none.  required=False (fused_head_multi) checks the tables that are given and leaves the
+    mode and what is missing to the native check.  per_point (the counting form) takes G parameter sets -- logprior [G,C],
+    the Dirichlet tab [G,E,C,C] and lognorm [G,E,C], the Bayes tab shared -- and G is returned (1 otherwise)."""
+    if required:
+        if mode == 2:
+            if tab is not None or lognorm is not None or logprior is not None:
+                raise ValueError('the mean takes no tables')
+            return 1
+        if tab is None or logprior is None or (mode == 1 and lognorm is None):
+            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
+        if mode == 0 and lognorm is not None:
+            raise ValueError('Bayes fusion takes no lognorm')
+    G, lead = 1, ()
+    if per_point:
+        G = int(logprior.shape[0]) if logprior.dim() == 2 else 0
+        lead = (G,)
+    for name, t, shape in (('tab', tab, (lead if mode == 1 else ()) + (E, C, C)), ('lognorm', lognorm, lead + (E, C)),
+                           ('logprior', logprior, lead + (C,))):
+        if t is not None:
+            _need(t, torch.float32, name)
+            if G < 1 or tuple(t.shape) != shape:
+                raise ValueError('%s of shape %s, expected %s%s' % (name, tuple(t.shape), shape,
+                                                                    ' with G >= 1' if per_point else ''))
+    return G
 
 
 def fused_head_grid_capacity(num_classes):
@@ -743,28 +810,10 @@ def fused_head_multi(scores, biases, n, hi, wi, num_classes, mode, tab=None, log
     logprior, the labels of dirichlet_fuse on their probability maps; 2 / 'mean': no tables, the labels of average_fuse --
     bit for bit, and none of those maps is written."""
     mode = FUSED_HEAD_MODES.get(mode, mode)
-    scores, biases = list(scores), list(biases)
-    if len(scores) != len(biases):
-        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
-    cp = (int(num_classes) + 3) // 4 * 4
-    for i, (S, b) in enumerate(zip(scores, biases)):
-        _need(S, torch.float32, 'scores[%d]' % i)
-        _need(b, torch.float32, 'biases[%d]' % i)
-        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
-            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
-        if b.numel() != int(num_classes):
-            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), int(num_classes)))
-    e, c = len(scores), int(num_classes)
-    for name, t, shape in (('tab', tab, (e, c, c)), ('lognorm', lognorm, (e, c)), ('logprior', logprior, (c,))):
-        if t is not None:
-            _need(t, torch.float32, name)
-            if tuple(t.shape) != shape:
-                raise ValueError('%s of shape %s, expected %s' % (name, tuple(t.shape), shape))
-    if out is None:
-        out = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.int64, device=scores[0].device)
-    elif out.dtype != torch.int64 or out.numel() != n * hi * wi * 64:
-        raise ValueError('out must be int64 of %d elements' % (n * hi * wi * 64))
-    rc = _lib.lib().xv_fused_head_multi_fwd(_ptr_array(scores), _ptr_array(biases), e, int(n), int(hi), int(wi), c, int(mode),
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes)
+    _check_fusion_tables(mode, E, C, tab, lognorm, logprior, required=False)
+    out = _label_output(out, n, hi, wi, scores[0].device)
+    rc = _lib.lib().xv_fused_head_multi_fwd(_ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C, int(mode),
                                            _ptr(tab), _ptr(lognorm), _ptr(logprior), _ptr(out), _stream())
     _lib.check(rc, 'xv_fused_head_multi_fwd')
     return out
@@ -788,45 +837,13 @@ def fused_head_multi_count(scores, biases, n, hi, wi, num_classes, mode, labels,
     mode = FUSED_HEAD_MODES.get(mode, mode)
     if mode not in (0, 1, 2):
         raise ValueError('unknown fused head mode %r' % (mode,))
-    scores, biases = list(scores), list(biases)
-    if len(scores) != len(biases):
-        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
-    E, C, NG = len(scores), int(num_classes), int(num_groups)
-    cp = (C + 3) // 4 * 4
-    for i, (S, b) in enumerate(zip(scores, biases)):
-        _need(S, torch.float32, 'scores[%d]' % i)
-        _need(b, torch.float32, 'biases[%d]' % i)
-        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
-            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
-        if b.numel() != C:
-            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
-    _need(labels, torch.int32, 'labels')
-    if labels.numel() != n * hi * wi * 64:
-        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
-    if mode == 2:
-        if tab is not None or lognorm is not None or logprior is not None:
-            raise ValueError('the mean takes no tables')
-        G = 1
-    else:
-        if tab is None or logprior is None or (mode == 1 and lognorm is None):
-            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
-        G = int(logprior.shape[0]) if logprior.dim() == 2 else 0
-        shapes = ((('tab', tab, (E, C, C)),) if mode == 0 else (('tab', tab, (G, E, C, C)), ('lognorm', lognorm, (G, E, C))))
-        for name, t, shape in shapes + (('logprior', logprior, (G, C)),):
-            _need(t, torch.float32, name)
-            if G < 1 or tuple(t.shape) != shape:
-                raise ValueError('%s of shape %s, expected %s with G >= 1' % (name, tuple(t.shape), shape))
-    ids = None
-    if groups is not None:
-        ids = _group_ids(groups, n, NG, scores[0].device)
-    elif NG != 1:
-        raise ValueError('num_groups = %d without groups' % NG)
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes)
+    _check_labels(labels, n, hi, wi)
+    # (a lognorm handed to the Bayes form is ignored, as it always was)
+    G = _check_fusion_tables(mode, E, C, tab, lognorm if mode != 0 else None, logprior, per_point=True)
+    NG = int(num_groups)
+    cm, ids = _grouped_output(cm, 'cm', groups, n, NG, (G, C, C), scores[0].device)
     lead = (NG,) if groups is not None else ()
-    if cm is None:
-        cm = torch.zeros(lead + (G, C, C), dtype=torch.int64, device=scores[0].device)
-    _need(cm, torch.int64, 'cm')
-    if tuple(cm.shape) != lead + (G, C, C):
-        raise ValueError('cm of shape %s, expected %s' % (tuple(cm.shape), lead + (G, C, C)))
     if expert_cm is not None:
         _need(expert_cm, torch.int64, 'expert_cm')
         if tuple(expert_cm.shape) != lead + (E, C, C):
@@ -850,24 +867,6 @@ def fused_head_multi_count(scores, biases, n, hi, wi, num_classes, mode, labels,
     return cm
 
 
-def _agreement_table_arg(table, groups, n, num_groups, num_classes, num_experts, device):
-    """(table, group ids) of the two agreement ops: int64 [num_groups, C, 2^E, 2, 3], or [C, 2^E, 2, 3] without groups; a zeroed
-    one is made here when none is given."""
-    NG = int(num_groups)
-    ids = None
-    if groups is not None:
-        ids = _group_ids(groups, n, NG, device)
-    elif NG != 1:
-        raise ValueError('num_groups = %d without groups' % NG)
-    shape = ((NG,) if groups is not None else ()) + (int(num_classes), 1 << int(num_experts), 2, 3)
-    if table is None:
-        table = torch.zeros(shape, dtype=torch.int64, device=device)
-    _need(table, torch.int64, 'table')
-    if tuple(table.shape) != shape:
-        raise ValueError('table of shape %s, expected %s' % (tuple(table.shape), shape))
-    return table, ids
-
-
 def fused_head_multi_agreement(scores, biases, n, hi, wi, num_classes, mode, labels, tab=None, lognorm=None, logprior=None,
                                groups=None, num_groups=1, table=None, max_workgroups=0):
     """Two to four experts' low-resolution scores (as fused_head_multi takes them, with its tables for `mode`) -> the
@@ -880,37 +879,10 @@ def fused_head_multi_agreement(scores, biases, n, hi, wi, num_classes, mode, lab
     mode = FUSED_HEAD_MODES.get(mode, mode)
     if mode not in (0, 1, 2):
         raise ValueError('unknown fused head mode %r' % (mode,))
-    scores, biases = list(scores), list(biases)
-    if len(scores) != len(biases):
-        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
-    E, C = len(scores), int(num_classes)
-    if not 2 <= E <= 4:
-        raise ValueError('the agreement head takes two to four experts, got %d' % E)
-    cp = (C + 3) // 4 * 4
-    for i, (S, b) in enumerate(zip(scores, biases)):
-        _need(S, torch.float32, 'scores[%d]' % i)
-        _need(b, torch.float32, 'biases[%d]' % i)
-        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
-            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
-        if b.numel() != C:
-            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
-    _need(labels, torch.int32, 'labels')
-    if labels.numel() != n * hi * wi * 64:
-        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
-    if mode == 2:
-        if tab is not None or lognorm is not None or logprior is not None:
-            raise ValueError('the mean takes no tables')
-    else:
-        if tab is None or logprior is None or (mode == 1 and lognorm is None):
-            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
-        if mode == 0 and lognorm is not None:
-            raise ValueError('Bayes fusion takes no lognorm')
-        for name, t, shape in (('tab', tab, (E, C, C)), ('lognorm', lognorm, (E, C)), ('logprior', logprior, (C,))):
-            if t is not None:
-                _need(t, torch.float32, name)
-                if tuple(t.shape) != shape:
-                    raise ValueError('%s of shape %s, expected %s' % (name, tuple(t.shape), shape))
-    table, ids = _agreement_table_arg(table, groups, n, num_groups, C, E, scores[0].device)
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes, 'the agreement head')
+    _check_labels(labels, n, hi, wi)
+    _check_fusion_tables(mode, E, C, tab, lognorm, logprior)
+    table, ids = _grouped_output(table, 'table', groups, n, num_groups, (C, 1 << E, 2, 3), scores[0].device)
     rc = _lib.lib().xv_fused_head_multi_agreement_fwd(
         _ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C, int(mode), _ptr(tab), _ptr(lognorm),
         _ptr(logprior), _ptr(labels), _ptr(ids), int(num_groups), _ptr(table), int(max_workgroups), _stream())
@@ -936,7 +908,7 @@ def agreement_table(labels, expert_labels, fused, num_classes, groups=None, num_
         if t.shape != labels.shape:
             raise ValueError('%s of shape %s, labels of shape %s' % (name, tuple(t.shape), tuple(labels.shape)))
     n = labels.shape[0]
-    table, ids = _agreement_table_arg(table, groups, n, num_groups, C, E, labels.device)
+    table, ids = _grouped_output(table, 'table', groups, n, num_groups, (C, 1 << E, 2, 3), labels.device)
     rc = _lib.lib().xv_agreement_table(_ptr(labels), _ptr_array(expert_labels), E, _ptr(fused), _ptr(ids), n,
                                        labels.numel() // n, C, int(num_groups), _ptr(table), _stream())
     _lib.check(rc, 'xv_agreement_table')
@@ -1050,36 +1022,9 @@ def fused_head_multi_calibration(scores, biases, n, hi, wi, num_classes, mode, l
     if mode not in (0, 1, 2):
         raise ValueError('unknown fused head mode %r' % (mode,))
     temps, NB = _calibration_temperatures(temperatures, bin_bits)
-    scores, biases = list(scores), list(biases)
-    if len(scores) != len(biases):
-        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
-    E, C = len(scores), int(num_classes)
-    if not 2 <= E <= 4:
-        raise ValueError('the calibration head takes two to four experts, got %d' % E)
-    cp = (C + 3) // 4 * 4
-    for i, (S, b) in enumerate(zip(scores, biases)):
-        _need(S, torch.float32, 'scores[%d]' % i)
-        _need(b, torch.float32, 'biases[%d]' % i)
-        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
-            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
-        if b.numel() != C:
-            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
-    _need(labels, torch.int32, 'labels')
-    if labels.numel() != n * hi * wi * 64:
-        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
-    if mode == 2:
-        if tab is not None or lognorm is not None or logprior is not None:
-            raise ValueError('the mean takes no tables')
-    else:
-        if tab is None or logprior is None or (mode == 1 and lognorm is None):
-            raise ValueError('mode %d needs tab and logprior%s' % (mode, ', lognorm' if mode == 1 else ''))
-        if mode == 0 and lognorm is not None:
-            raise ValueError('Bayes fusion takes no lognorm')
-        for name, t, shape in (('tab', tab, (E, C, C)), ('lognorm', lognorm, (E, C)), ('logprior', logprior, (C,))):
-            if t is not None:
-                _need(t, torch.float32, name)
-                if tuple(t.shape) != shape:
-                    raise ValueError('%s of shape %s, expected %s' % (name, tuple(t.shape), shape))
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes, 'the calibration head')
+    _check_labels(labels, n, hi, wi)
+    _check_fusion_tables(mode, E, C, tab, lognorm, logprior)
     device, NT, grouped = scores[0].device, len(temps), groups is not None
     table, nll, ids = _calibration_outputs(table, nll, 'table', groups, n, num_groups, (), NT, NB, device)
     experts = bool(experts) or expert_table is not None or expert_nll is not None
@@ -1111,20 +1056,7 @@ def tuple_capacity(num_classes, num_experts):
 
 def _check_tuple_experts(scores, biases, n, hi, wi, num_classes, what):
     """(scores, biases, E, C, T) of a label-tuple head, the shapes checked as fused_head_multi checks them."""
-    scores, biases = list(scores), list(biases)
-    if len(scores) != len(biases):
-        raise ValueError('%d score tensors but %d biases' % (len(scores), len(biases)))
-    E, C = len(scores), int(num_classes)
-    if not 2 <= E <= 4:
-        raise ValueError('%s takes two to four experts, got %d' % (what, E))
-    cp = (C + 3) // 4 * 4
-    for i, (S, b) in enumerate(zip(scores, biases)):
-        _need(S, torch.float32, 'scores[%d]' % i)
-        _need(b, torch.float32, 'biases[%d]' % i)
-        if tuple(S.shape) != (n, hi + 2, wi + 2, cp):
-            raise ValueError('low-resolution scores %d of shape %s, expected %s' % (i, tuple(S.shape), (n, hi + 2, wi + 2, cp)))
-        if b.numel() != C:
-            raise ValueError('bias %d of %d values, expected %d' % (i, b.numel(), C))
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes, what)
     if not 2 <= C <= 32 or not tuple_capacity(C, E):
         raise ValueError('%s does not serve %d experts at %d classes (tuple_capacity)' % (what, E, C))
     return scores, biases, E, C, C ** E
@@ -1173,10 +1105,7 @@ def fused_head_multi_lut(scores, biases, n, hi, wi, num_classes, lut, out=None):
     tuples decides, lut uint8 [C^E], in one launch: out = lut[t]."""
     scores, biases, E, C, T = _check_tuple_experts(scores, biases, n, hi, wi, num_classes, 'the lookup head')
     _check_tuple_lut(lut, T)
-    if out is None:
-        out = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.int64, device=scores[0].device)
-    elif out.dtype != torch.int64 or out.numel() != n * hi * wi * 64:
-        raise ValueError('out must be int64 of %d elements' % (n * hi * wi * 64))
+    out = _label_output(out, n, hi, wi, scores[0].device)
     rc = _lib.lib().xv_fused_head_multi_lut_fwd(_ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C,
                                                _ptr(lut), _ptr(out), _stream())
     _lib.check(rc, 'xv_fused_head_multi_lut_fwd')
@@ -1190,9 +1119,7 @@ def fused_head_multi_lut_count(scores, biases, n, hi, wi, num_classes, lut, labe
     zeroed, when None) and returns it."""
     scores, biases, E, C, T = _check_tuple_experts(scores, biases, n, hi, wi, num_classes, 'the counting lookup head')
     _check_tuple_lut(lut, T)
-    _need(labels, torch.int32, 'labels')
-    if labels.numel() != n * hi * wi * 64:
-        raise ValueError('labels of shape %s, expected %s' % (tuple(labels.shape), (n, 8 * hi, 8 * wi)))
+    _check_labels(labels, n, hi, wi)
     cm, ids = _grouped_output(cm, 'cm', groups, n, num_groups, (C, C), scores[0].device)
     rc = _lib.lib().xv_fused_head_multi_lut_count_fwd(_ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C,
                                                      _ptr(lut), _ptr(labels), _ptr(ids), int(num_groups), _ptr(cm),
