@@ -652,7 +652,38 @@ int xv_fused_head_multi_calibration_fwd(const float* const* S, const float* cons
                                         double* nll, int64_t* expert_table, double* expert_nll, int max_workgroups,
                                         void* stream);
 
-/* ---- label-tuple heads (csrc/tuple_lut.hip) ----------------------------------------------------------------------------------
+/* ---- confidence maps (csrc/confidence.hip) -----------------------------------------------------------------------------------
+ * The confidence the calibration tables count, handed out per pixel.  For class scores s[k], k < C (2..32), in the log domain
+ * and their first maximum `win`, as the calibration section takes them, at ONE temperature T > 0:
+ *   d_k = (s[k] - s[win]) / T, e_k = exp(d_k), z = sum_k e_k (ascending k), conf = 1 / z           (the statements of the tables)
+ *   entropy = max(0, ln z - (sum_k e_k d_k) / z)   in nats; a term with e_k = 0 adds nothing
+ *   margin  = conf - (max_{k != win} e_k) / z      in [0, 1]; 0 where the maximum is tied
+ *   label   = conf < threshold ? void_label : win  threshold 0: nothing is void
+ * (uint32)(conf 2^24) of a written confidence is exactly the q of xv_calibration_table on the same scores.  Outputs: label_out
+ * int64 (8-byte aligned), conf_out, entropy_out, margin_out float32 (4-byte aligned), one entry per pixel; each may be NULL and
+ * is then not touched; at least one is given.  A thread takes one pixel; the grid is eight 256-thread workgroups per CU at most.
+ *
+ * xv_confidence_map, from a MATERIALISED map: values float32 [n][ppi][C] (4-byte aligned), kind 0 = class scores, kind 1 =
+ * probabilities, mapped to ln(1e-20 + p) after `win` is taken as their first maximum.  XV_EINVAL, with nothing launched and
+ * every output untouched, for a temperature that is not finite and positive, a threshold that is not finite or outside [0, 1],
+ * num_classes outside 2..32, an unknown kind, n or ppi below 1, all four outputs NULL, or a null or misaligned pointer.       */
+int xv_confidence_map(const float* values, int kind, int n, int64_t ppi, int num_classes, float temperature, float threshold,
+                      int64_t void_label, int64_t* label_out, float* conf_out, float* entropy_out, float* margin_out,
+                      void* stream);
+
+/* The same maps from the experts' low-resolution scores, in one launch: S, bias, num_experts (2..4), n, hi, wi, num_classes,
+ * mode (0 Bayes, 1 Dirichlet, 2 mean), tab, lognorm and logprior as xv_fused_head_multi_calibration_fwd takes them; outputs
+ * [n][8 hi][8 wi].  The fused scores are those of the fusion kernels on the maps xv_decoder_head_fwd writes; with threshold 0
+ * label_out is the label xv_fused_head_multi_fwd writes, bit for bit.  No probability or score map is written.  XV_EINVAL, with
+ * nothing launched and every output untouched, as above (hi or wi below 1 too) and as xv_fused_head_multi_agreement_fwd
+ * refuses its experts, mode and tables.                                                                                        */
+int xv_fused_head_multi_confidence_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi, int wi,
+                                       int num_classes, int mode, const float* tab, const float* lognorm,
+                                       const float* logprior, float temperature, float threshold, int64_t void_label,
+                                       int64_t* label_out, float* conf_out, float* entropy_out, float* margin_out,
+                                       void* stream);
+
+/* ---- label-tuple heads (csrc/tuple_lut.hip)----------------------------------------------------------------------------------
  * For a fusion that sees a pixel only through the tuple of its experts' labels (IBCC: modular_semantic_segmentation_amd/ibcc.py).
  * S, bias, num_experts (2..4), n, hi, wi and num_classes (2..32) as xv_fused_head_multi_fwd takes them.  The tuple index of a
  * pixel is t = ((l_0 C + l_1) C + l_2) ..., expert 0 most significant, T = C^E tuples -- the row-major index of a [C]*E

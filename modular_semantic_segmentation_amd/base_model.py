@@ -529,6 +529,50 @@ class BaseModel(object):
         measures = [self._calibration_results(counts, 0, t, num_bins, False)[0] for t in range(len(temps))]
         return {'temperatures': temps, 'measures': measures, 'tables': counts[0][0], 'best': best_temperature(temps, measures)}
 
+    # ---- confidence maps: the label and how far to trust it, per pixel (csrc/confidence.hip) -------------------------------
+    def _confidence_batch(self, batch, temperature, want, threshold, void_label):
+        """One batch of predict_confidence: the model's class scores, materialised, through ops.confidence_map -> {key: device
+        tensor [N, H, W]} for the keys of `want`.  A fusion model overrides it."""
+        from . import ops
+        score = self._predict_batch_impl(batch, output_attr='score')
+        C = self.config['num_classes']
+        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or score.dim() != 4 or score.shape[-1] != C:
+            raise NotImplementedError('%s.predict_confidence: the model has no class-score output' % type(self).__name__)
+        return ops.confidence_map(score.contiguous(), temperature, kind=0, want=want, threshold=threshold,
+                                  void_label=void_label)
+
+    def predict_confidence(self, data, temperature=None, outputs=('confidence',), threshold=None, void_label=-1):
+        """The label of predict() with how far to trust it, as numpy arrays: {'label': int64 [N, H, W], and float32 [N, H, W]
+        for every name in `outputs`, from 'confidence' (the posterior of the label at `temperature`, the confidence
+        score_calibration counts: int(confidence 2^24) is its q), 'entropy' (of that posterior, in nats) and 'margin' (the
+        confidence minus the second largest probability)}.  temperature None: config['temperature'] (fit_temperature stores
+        it), else 1.  With a `threshold` in [0, 1] the label is `void_label` where the confidence is below it; without one it
+        equals predict(data).  The posterior is that of the class scores the model decides by, as score_calibration has it; the
+        models it refuses are refused here (NotImplementedError).  The batches run eagerly, one after the other."""
+        refusal = self._calibration_refusal()
+        if refusal is not None:
+            raise NotImplementedError('%s.predict_confidence: %s' % (type(self).__name__, refusal))
+        outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        if len(set(outputs)) != len(outputs) or any(k not in ('confidence', 'entropy', 'margin') for k in outputs):
+            raise ValueError("outputs names 'confidence', 'entropy' or 'margin', each once; got %r" % (outputs,))
+        T = float(self.config.get('temperature', 1.0) if temperature is None else temperature)
+        want = ('label',) + outputs
+        parts = {k: [] for k in want}
+        for batch in iterate_batches(data, self.config['batchsize']):
+            maps = self._confidence_batch(batch, T, want, 0.0 if threshold is None else float(threshold), int(void_label))
+            for k in want:
+                parts[k].append(maps[k].cpu().numpy())
+        return {k: np.concatenate(v) for k, v in parts.items()}
+
+    def fit_temperature(self, data, temperatures=None):
+        """calibration_search over `temperatures` (default: nine from 0.25 to 4, a factor sqrt 2 apart) on one pass over the
+        labelled `data`; the temperature of least NLL becomes config['temperature'], the default of predict_confidence.
+        Returns what calibration_search returns."""
+        temps = np.geomspace(0.25, 4.0, 9) if temperatures is None else temperatures
+        search = self.calibration_search(data, [float(t) for t in temps])
+        self.config['temperature'] = search['best']
+        return search
+
     # ---- weights ----------------------------------------------------------------------------------------
     def _variables_changed(self):
         """Called after self.variables was modified; subclasses re-upload to the GPU.  The engines allocate

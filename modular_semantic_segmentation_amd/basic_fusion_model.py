@@ -642,6 +642,20 @@ class FusionModel(BaseModel):
                     expert_into['expert_table'][:, e] += part
                     expert_into['expert_nll'][:, e] += part_nll
 
+    def _confidence_batch(self, batch, temperature, want, threshold, void_label):
+        """The routes of _calibrate_batch: where a fused head serves the model ONE ops.fused_head_multi_confidence launch after
+        the trunks writes the maps; otherwise the experts' outputs are materialised, fused by the model's own kernel with its
+        score output (the mean: its probabilities, kind 1) and handed to ops.confidence_map."""
+        from . import ops
+        C = self.config['num_classes']
+        into = dict(want=want, threshold=threshold, void_label=void_label)
+        head = self._agreement_head()
+        if head is not None and (fused_head_applicable(self) or multi_head_applicable(self)):
+            return ops.fused_head_multi_confidence(*run_lowres_scores_multi(self, batch), C, head[0], temperature, **head[1],
+                                                   **into)
+        values, kind = self._calibration_values(run_experts(self, batch, self.expert_wants))
+        return ops.confidence_map(values.contiguous(), temperature, kind=kind, **into)
+
     def prediction_difference(self, data):
         """The fused prediction beside every branch's own (dirichlet_mix.py:275-294, uncertainty_dirichlet_mix.py:424-443), as
         numpy arrays: {'fused_label' int64 [N,H,W], 'fused_score' float32 [N,H,W,C], and per modality m '<m>_prob' float32

@@ -114,3 +114,55 @@ def calibration_measures(table, nll, num_bins=15):
 def best_temperature(temperatures, measures):
     """The temperature of least NLL among `measures` (one calibration_measures result per temperature; the first on ties)."""
     return float(temperatures[int(np.argmin([m['NLL'] for m in measures]))])
+
+
+def confidence_reference(values, temperature, kind=0):
+    """The maps of csrc/confidence.hip in float64: values [..., C] (kind 0: scores in the log domain; kind 1: probabilities,
+    whose winner is taken first and which then become ln(1e-20 + p)) at ONE temperature T > 0.  Returns (label int64 [...], the
+    first maximum; confidence = 1 / z with z = sum_k e_k, e_k = exp(d_k), d_k = (s[k] - s[label]) / T; entropy = max(0, ln z -
+    (sum_k e_k d_k) / z) in nats, a term with e_k = 0 adding nothing; margin = confidence - max_{k != label} e_k / z)."""
+    v = np.asarray(values, np.float64)
+    T = float(temperature)
+    if not (np.isfinite(T) and T > 0):
+        raise ValueError('the temperature must be finite and positive, got %r' % (temperature,))
+    if kind not in (0, 1):
+        raise ValueError('kind must be 0 or 1, got %r' % (kind,))
+    if v.ndim < 1 or v.shape[-1] < 2:
+        raise ValueError('values of shape %s, expected [..., C] with C >= 2' % (v.shape,))
+    win = np.argmax(v, -1)                                  # (numpy's argmax is the first maximum)
+    s = np.log(np.float64(np.float32(1e-20)) + v) if kind == 1 else v
+    d = (s - np.take_along_axis(s, win[..., None], -1)) / T
+    e = np.exp(d)
+    z = e.sum(-1)
+    with np.errstate(invalid='ignore'):
+        ed = np.where(e > 0, e * d, 0.0).sum(-1)
+    others = np.where(np.arange(v.shape[-1]) == win[..., None], -np.inf, e)
+    conf = 1.0 / z
+    return win.astype(np.int64), conf, np.maximum(np.log(z) - ed / z, 0.0), conf - others.max(-1) / z
+
+
+def risk_coverage(table):
+    """Selective prediction read off ONE reliability table (int [NB, 3]): keeping only the pixels whose fixed-point confidence
+    q is at least j 2^24 / NB -- what a confidence map's threshold j / NB keeps, the lower edge of bin j -- for every j < NB:
+      thresholds [NB]  j / NB
+      coverage   [NB]  the share of the counted pixels that is kept (the bins j and above)
+      risk       [NB]  1 - accuracy among the kept ones; NaN where none is kept
+      area             the area under risk over coverage by the trapezoid rule, the curve continued flat from its smallest
+                       coverage down to 0 (a constant risk gives that risk); NaN for a table without pixels
+    The counts are integers, so coverage and risk are exact ratios of them."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError('calibration table of shape %s, expected [NB, 3]' % (t.shape,))
+    NB = t.shape[0]
+    kept = np.cumsum(t[::-1, 0].astype(np.int64))[::-1]
+    right = np.cumsum(t[::-1, 1].astype(np.int64))[::-1]
+    N = int(kept[0])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        coverage = kept / np.float64(N) if N > 0 else np.full(NB, np.nan)
+        risk = np.where(kept > 0, 1.0 - right / kept.astype(np.float64), np.nan)
+    area = float('nan')
+    if N > 0:
+        keep = kept > 0
+        c, r = coverage[keep][::-1], risk[keep][::-1]       # ascending coverage
+        area = float(c[0] * r[0] + ((c[1:] - c[:-1]) * (r[1:] + r[:-1]) / 2).sum())
+    return {'thresholds': np.arange(NB) / float(NB), 'coverage': coverage, 'risk': risk, 'area': area}

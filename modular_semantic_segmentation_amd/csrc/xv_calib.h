@@ -54,6 +54,25 @@ __device__ static __forceinline__ float calib_pick(const float (&s)[CM], int idx
   return v;
 }
 
+// One class's term of z and its exponent d = (s[k] - s[win]) / T; calib_conf: the confidence of a finished z.  The two
+// statements calib_pixel and conf_pixel (xv_conf.h) share: a confidence map's q IS the q counted here.
+__device__ static __forceinline__ float calib_term(float s_k, float s_win, float T, float& d) {
+#pragma clang fp contract(off)
+  d = (s_k - s_win) / T;
+  return xv_fast_exp(d);
+}
+
+__device__ static __forceinline__ float calib_conf(float z) {
+#pragma clang fp contract(off)
+  return 1.0f / z;
+}
+
+// the fixed-point confidence: truncation, 0 <= q <= 2^24 whatever conf holds (NaN gives 0)
+__device__ static __forceinline__ uint32_t calib_q(float conf) {
+#pragma clang fp contract(off)
+  return (uint32_t)fminf(fmaxf(conf * 16777216.f, 0.f), 16777216.f);
+}
+
 // One pixel at one temperature: s_win = s[win], s_lab = s[label] (calib_pick, taken once per pixel by the caller; s_lab is
 // ignored by a caller that drops nll).  Lanes k >= C are ignored.
 template <int CM>
@@ -63,9 +82,11 @@ __device__ static __forceinline__ void calib_pixel(const float (&s)[CM], int C, 
   float z = 0.f;
 #pragma unroll
   for (int k = 0; k < CM; ++k)
-    if (k < C) z = z + xv_fast_exp((s[k] - s_win) / T);
-  const float conf = 1.0f / z;
-  q = (uint32_t)fminf(fmaxf(conf * 16777216.f, 0.f), 16777216.f);
+    if (k < C) {
+      float d;
+      z = z + calib_term(s[k], s_win, T, d);
+    }
+  q = calib_q(calib_conf(z));
   const int top = (1 << bin_bits) - 1;
   const int b = (int)(q >> (24 - bin_bits));
   bin = b < top ? b : top;

@@ -132,6 +132,11 @@ class DirichletFusion(FusionModel):
             raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
         return FusionModel._calibrate_batch(self, *args, **kwargs)
 
+    def _confidence_batch(self, *args, **kwargs):
+        if not hasattr(self, 'am1'):
+            raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')
+        return FusionModel._confidence_batch(self, *args, **kwargs)
+
     def _prediction_difference_batch(self, batch):
         if not hasattr(self, 'am1'):
             raise UserWarning('ERROR: DirichletFusion has no measurements yet, call fit() first')

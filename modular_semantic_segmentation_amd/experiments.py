@@ -111,6 +111,31 @@ def evaluate_calibration(net, testset, temperatures=None, print_results=True):
     return result + (search,) if search is not None else result
 
 
+def evaluate_confidence(net, testset, thresholds, temperature=None, print_results=True):
+    """What abstaining below a confidence threshold buys: for every threshold the coverage (share of the labelled pixels
+    net.predict_confidence(threshold=...) would keep) and the risk (share of wrong labels among them), read off ONE
+    net.score_calibration pass (calibration.risk_coverage of its table of 1024 bins) at `temperature` -- by default the one
+    fit_temperature stored, else 1.  A threshold is served at the bin edge at or above it, exact for multiples of 1/1024.
+    Returns {'thresholds': the edges used, 'coverage', 'risk' (arrays, one entry per threshold), 'area': the area under the
+    whole risk-coverage curve, 'measures': the calibration measures}."""
+    from .calibration import risk_coverage
+    T = float(getattr(net, 'config', {}).get('temperature', 1.0) if temperature is None else temperature)
+    measures, table = net.score_calibration(testset, temperature=T)[:2]
+    curve = risk_coverage(table)
+    NB = len(curve['thresholds'])
+    edges = np.minimum(np.ceil(np.asarray(thresholds, np.float64) * NB).astype(np.int64), NB - 1)
+    if (edges < 0).any():
+        raise ValueError('thresholds lie in [0, 1], got %r' % (thresholds,))
+    result = {'thresholds': curve['thresholds'][edges], 'coverage': curve['coverage'][edges], 'risk': curve['risk'][edges],
+              'area': curve['area'], 'measures': measures}
+    if print_results:
+        print('temperature {:g}: accuracy {:.3f} confidence {:.3f} area under risk-coverage {:.4f}'.format(
+            T, measures['accuracy'], measures['mean_confidence'], curve['area']))
+        for t, c, r in zip(result['thresholds'], result['coverage'], result['risk']):
+            print('{:>15}: coverage {:.3f} risk {:.4f}'.format('conf >= %.4g' % t, c, r))
+    return result
+
+
 def evaluate_on_all_sequences(net, testset, sequence_of_image):
     """experiments/evaluation.py:42-55 (evaluate_on_all_synthia_seqs) on one pass instead of one evaluation per sequence:
     sequence_of_image names the sequence of every image of `testset`, in order.  Returns {sequence: measures}."""

@@ -1046,6 +1046,75 @@ def fused_head_multi_calibration(scores, biases, n, hi, wi, num_classes, mode, l
     return (table, nll, expert_table, expert_nll) if experts else (table, nll)
 
 
+# ---- confidence maps (csrc/confidence.hip): the confidence the tables above count, written per pixel at one temperature
+
+CONFIDENCE_MAPS = {'label': torch.int64, 'confidence': torch.float32, 'entropy': torch.float32, 'margin': torch.float32}
+
+
+def _confidence_outputs(want, out, shape, device, temperature, threshold):
+    """{key: tensor} of the maps in `want` (from label, confidence, entropy, margin; at least one), taken from `out` where it
+    holds them, made here otherwise, and the temperature and threshold checked as the kernels check them."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(k not in CONFIDENCE_MAPS for k in want):
+        raise ValueError('want names one or more of %s, each once, got %r' % (', '.join(CONFIDENCE_MAPS), want))
+    T, thr = float(temperature), float(threshold)
+    if not (np.isfinite(T) and np.float32(T) > 0 and np.isfinite(np.float32(T))):
+        raise ValueError('the temperature must be finite and positive, got %r' % (temperature,))
+    if not 0.0 <= thr <= 1.0:
+        raise ValueError('the threshold must lie in [0, 1], got %r' % (threshold,))
+    maps = {}
+    for k in want:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=CONFIDENCE_MAPS[k], device=device)
+        _need(t, CONFIDENCE_MAPS[k], 'out[%r]' % k)
+        if t.numel() != int(np.prod(shape)):
+            raise ValueError('out[%r] of shape %s, expected %s' % (k, tuple(t.shape), tuple(shape)))
+        maps[k] = t
+    return maps, T, thr
+
+
+def confidence_map(values, temperature=1.0, kind=0, want=('label', 'confidence'), threshold=0.0, void_label=-1, out=None):
+    """A MATERIALISED map -- values float32 [n, ..., C], class scores in the log domain (kind 0) or probabilities (kind 1:
+    ln(1e-20 + p) after the winner is taken) -- to {key: device tensor [n, ...]} for the keys of `want`: 'label' int64, the
+    first maximum, or void_label where the confidence is below `threshold`; 'confidence' = 1 / sum_k exp((s[k] - s[win]) / T),
+    whose int(conf 2^24) is the q calibration_table counts; 'entropy' of that softmax in nats; 'margin', the confidence minus
+    the second largest probability.  `out` may hold tensors to write into."""
+    if kind not in (0, 1):
+        raise ValueError('kind must be 0 (scores) or 1 (probabilities), got %r' % (kind,))
+    _need(values, torch.float32, 'values')
+    if values.dim() < 2 or values.numel() == 0 or not 2 <= int(values.shape[-1]) <= 32:
+        raise ValueError('values of shape %s, expected non-empty [n, ..., C] with 2..32 classes' % (tuple(values.shape),))
+    shape, C = tuple(values.shape[:-1]), int(values.shape[-1])
+    maps, T, thr = _confidence_outputs(want, out, shape, values.device, temperature, threshold)
+    n = shape[0]
+    rc = _lib.lib().xv_confidence_map(_ptr(values), int(kind), n, values.numel() // (n * C), C, T, thr, int(void_label),
+                                      _ptr(maps.get('label')), _ptr(maps.get('confidence')), _ptr(maps.get('entropy')),
+                                      _ptr(maps.get('margin')), _stream())
+    _lib.check(rc, 'xv_confidence_map')
+    return maps
+
+
+def fused_head_multi_confidence(scores, biases, n, hi, wi, num_classes, mode, temperature=1.0, tab=None, lognorm=None,
+                                logprior=None, want=('label', 'confidence'), threshold=0.0, void_label=-1, out=None):
+    """Two to four experts' low-resolution scores (as fused_head_multi takes them, with its tables for `mode`) -> the maps of
+    confidence_map for the FUSED posterior, [n, 8hi, 8wi] each, in one launch: what confidence_map gives on the fused score
+    map (Bayes, Dirichlet) or the mean probabilities (kind 1), without that map.  With threshold 0 'label' is the label of
+    fused_head_multi, bit for bit."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError('unknown fused head mode %r' % (mode,))
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes, 'the confidence head')
+    _check_fusion_tables(mode, E, C, tab, lognorm, logprior)
+    maps, T, thr = _confidence_outputs(want, out, (n, 8 * hi, 8 * wi), scores[0].device, temperature, threshold)
+    rc = _lib.lib().xv_fused_head_multi_confidence_fwd(
+        _ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C, int(mode), _ptr(tab), _ptr(lognorm),
+        _ptr(logprior), T, thr, int(void_label), _ptr(maps.get('label')), _ptr(maps.get('confidence')),
+        _ptr(maps.get('entropy')), _ptr(maps.get('margin')), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_confidence_fwd')
+    return maps
+
+
 # ---- label-tuple heads (csrc/tuple_lut.hip): the tuple of a pixel's expert labels is t = ((l_0 C + l_1) C + l_2) ..., expert
 # 0 most significant: the row-major index of a [C]*E decision array
 
