@@ -683,6 +683,41 @@ int xv_fused_head_multi_confidence_fwd(const float* const* S, const float* const
                                        int64_t* label_out, float* conf_out, float* entropy_out, float* margin_out,
                                        void* stream);
 
+/* ---- uncertainty benchmarks of a posterior (csrc/confidence_stats.hip) ------------------------------------------------------
+ * The counting form of the confidence maps: per pixel conf, entropy and margin as above, and three metrics, larger = less
+ * certain, each one IEEE float32 operation from a written map value, in this order:
+ *   entropy, least_confidence = 1.0f - conf, small_margin = 1.0f - margin.
+ * hist uint64 [3][2][octaves << mantissa_bits]: hist[metric][row][bin(value)] += 1, bin as xv_uncertainty_stats bins a metric
+ * (values at or below 2^(1 - octaves) share bin 0: with 24 octaves the resolution of 1 - conf in float32).  fixed_row = -1:
+ * row = (win != label) over the pixels with 0 <= label < C; fixed_row 0 or 1: that row for every pixel, and labels may be
+ * NULL.  With labels (int32, one per pixel), over the valid pixels, nll double [C]: nll[label] += nll_pixel of the calibration
+ * section at this temperature, and counts int64 [C]: counts[label] += 1.  Everything is accumulated, nothing cleared, no
+ * per-pixel map written.  The grid is two 512-thread workgroups per CU and never above 512; a workgroup counts in 32-bit LDS
+ * cells and flushes once, one 64-bit atomic per non-zero cell.
+ *
+ * xv_confidence_stats, from a MATERIALISED map: values, kind, n, ppi and num_classes as xv_confidence_map takes them.
+ * XV_EINVAL, with nothing launched and every table untouched, as xv_confidence_map refuses those and the temperature, for
+ * mantissa_bits outside 3..8, octaves outside 8..32, fixed_row outside {-1, 0, 1}, NULL labels with fixed_row = -1, NULL hist,
+ * NULL nll or counts with labels, a misaligned pointer (the tables 8 bytes, labels 4), or one table (the histograms and, with
+ * labels, 16 C bytes) above 64 KB.                                                                                             */
+int xv_confidence_stats(const float* values, int kind, int n, int64_t ppi, int num_classes, float temperature,
+                        const int32_t* labels, int mantissa_bits, int octaves, int fixed_row, uint64_t* hist, double* nll,
+                        int64_t* counts, void* stream);
+
+/* The same tables from the experts' low-resolution scores, in one launch: S, bias, num_experts (2..4), n, hi, wi, num_classes,
+ * mode, tab, lognorm and logprior as xv_fused_head_multi_confidence_fwd takes them, and its fused scores; labels int32
+ * [n][8 hi][8 wi].  expert_hist uint64 [E][3][2][bins], expert_nll double [E][C] and expert_counts int64 [E][C] (all NULL, or
+ * all given) take every expert's own tables from its interpolated logits, row = (that expert's label != label), as
+ * xv_fused_head_multi_calibration_fwd takes expert tables.  XV_EINVAL as above and as xv_fused_head_multi_confidence_fwd
+ * refuses its experts, mode and tables, for a partial set of expert outputs, and where the 1 + E tables and the staged fusion
+ * tables pass 160 KB.                                                                                                           */
+int xv_fused_head_multi_confidence_stats_fwd(const float* const* S, const float* const* bias, int num_experts, int n, int hi,
+                                             int wi, int num_classes, int mode, const float* tab, const float* lognorm,
+                                             const float* logprior, float temperature, const int32_t* labels,
+                                             int mantissa_bits, int octaves, int fixed_row, uint64_t* hist, double* nll,
+                                             int64_t* counts, uint64_t* expert_hist, double* expert_nll,
+                                             int64_t* expert_counts, void* stream);
+
 /* ---- label-tuple heads (csrc/tuple_lut.hip)----------------------------------------------------------------------------------
  * For a fusion that sees a pixel only through the tuple of its experts' labels (IBCC: modular_semantic_segmentation_amd/ibcc.py).
  * S, bias, num_experts (2..4), n, hi, wi and num_classes (2..32) as xv_fused_head_multi_fwd takes them.  The tuple index of a

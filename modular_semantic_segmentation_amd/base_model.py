@@ -15,6 +15,8 @@ import os
 import numpy as np
 import torch
 
+from .uncertainty_model import CONFIDENCE_METRICS, UncertaintyBenchmarks
+
 
 def iterate_batches(data, batchsize, max_batches=None):
     """Yield dicts of numpy arrays with a leading batch axis (<= batchsize samples each)."""
@@ -151,9 +153,11 @@ def reduce_over_ranks(model, *tensors):
         allreduce_sum_(*tensors)
 
 
-class BaseModel(object):
+class BaseModel(UncertaintyBenchmarks):
     """Handles IO, batching, scoring and weight files; subclasses implement `_build_graph`
-    (create engines / tables) and `_predict_batch`."""
+    (create engines / tables) and `_predict_batch`.  The uncertainty benchmarks (uncertainty_model.UncertaintyBenchmarks:
+    misclassification_detection_score, out_of_distribution_detection_score, nll_score, value_distribution,
+    uncertainty_tables, temperature_search) are served from the confidence of the model's class scores, see below."""
 
     required_attributes = [["loss"], ["prediction"]]
 
@@ -572,6 +576,40 @@ class BaseModel(object):
         search = self.calibration_search(data, [float(t) for t in temps])
         self.config['temperature'] = search['best']
         return search
+
+    # ---- uncertainty benchmarks of the posterior predict_confidence maps (csrc/confidence_stats.hip) ------------------------
+    # The hooks of uncertainty_model.UncertaintyBenchmarks: the metrics are ops.CONFIDENCE_METRICS at a temperature -- by default
+    # config['temperature_scaling'] if set, else config['temperature'] (fit_temperature stores it), else 1 -- and a batch costs its
+    # class scores once, counted by ONE ops.confidence_stats launch per temperature.  A fusion model overrides both.
+    uncertainty_metrics = CONFIDENCE_METRICS
+
+    def _default_temperature(self):
+        t = self.config.get('temperature_scaling')
+        return self.config.get('temperature', 1) if t is None else t
+
+    def _uncertainty_check(self):
+        refusal = self._calibration_refusal()
+        if refusal is not None:
+            raise NotImplementedError('%s: no uncertainty benchmarks: %s' % (type(self).__name__, refusal))
+
+    def _uncertainty_experts(self):
+        return self._calibration_experts()
+
+    def _uncertainty_state(self, batch, experts=False):
+        score = self._predict_batch_impl(batch, output_attr='score')
+        C = self.config['num_classes']
+        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or score.dim() != 4 or score.shape[-1] != C:
+            raise NotImplementedError('%s: no uncertainty benchmarks: the model has no class-score output' % type(self).__name__)
+        return {'values': score.contiguous(), 'kind': 0}
+
+    def _uncertainty_accumulate(self, state, labels, tables, temperature, fixed_row):
+        from . import ops
+        m, o = self._uncertainty_bins()
+        how = dict(temperature=temperature, fixed_row=fixed_row, mantissa_bits=m, octaves=o)
+        ops.confidence_stats(state['values'], labels, kind=state['kind'], tables={k: tables[k] for k in ('hist', 'nll', 'counts')},
+                             **how)
+        for e, values in enumerate(state.get('experts', ())):
+            ops.confidence_stats(values, labels, kind=0, tables={k: t[e] for k, t in tables['experts'].items()}, **how)
 
     # ---- weights ----------------------------------------------------------------------------------------
     def _variables_changed(self):

@@ -656,6 +656,35 @@ class FusionModel(BaseModel):
         values, kind = self._calibration_values(run_experts(self, batch, self.expert_wants))
         return ops.confidence_map(values.contiguous(), temperature, kind=kind, **into)
 
+    # ---- uncertainty benchmarks of the fused posterior (BaseModel's hooks; csrc/confidence_stats.hip) ----------------------
+    def _uncertainty_state(self, batch, experts=False):
+        """The routes of _confidence_batch: where a fused head serves the model the trunks stop at their low-resolution scores;
+        otherwise the experts' outputs are materialised and fused by the model's own kernel with its score output (the mean:
+        its probabilities, kind 1), with every expert's class scores beside them where its own tables are asked for."""
+        head = self._agreement_head()
+        if head is not None and (fused_head_applicable(self) or multi_head_applicable(self)):
+            return {'lowres': run_lowres_scores_multi(self, batch), 'head': head}
+        wants = tuple(dict.fromkeys(tuple(self.expert_wants) + (('score',) if experts else ())))
+        outs = run_experts(self, batch, wants)
+        values, kind = self._calibration_values(outs)
+        state = {'values': values.contiguous(), 'kind': kind}
+        if experts:
+            state['experts'] = [outs[m]['score'].contiguous() for m in self.modalities]
+        return state
+
+    def _uncertainty_accumulate(self, state, labels, tables, temperature, fixed_row):
+        """ONE ops.fused_head_multi_confidence_stats launch on the low-resolution scores -- the fusion's tables and, asked for,
+        every expert's; the materialised state is BaseModel's."""
+        if 'lowres' not in state:
+            return BaseModel._uncertainty_accumulate(self, state, labels, tables, temperature, fixed_row)
+        from . import ops
+        m, o = self._uncertainty_bins()
+        mode, head_tables = state['head']
+        ops.fused_head_multi_confidence_stats(*state['lowres'], self.config['num_classes'], mode, labels, temperature,
+                                              fixed_row=fixed_row, mantissa_bits=m, octaves=o,
+                                              tables={k: tables[k] for k in ('hist', 'nll', 'counts')},
+                                              expert_tables=tables.get('experts'), **head_tables)
+
     def prediction_difference(self, data):
         """The fused prediction beside every branch's own (dirichlet_mix.py:275-294, uncertainty_dirichlet_mix.py:424-443), as
         numpy arrays: {'fused_label' int64 [N,H,W], 'fused_score' float32 [N,H,W,C], and per modality m '<m>_prob' float32

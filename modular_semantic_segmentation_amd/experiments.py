@@ -347,6 +347,36 @@ def measure_metrics(net, data, metrics):
     return ret
 
 
+def evaluate_fusion_uncertainty(net, testset, ood_set=None, print_results=True):
+    """evaluate_uncertainty for the question a modular fusion exists to answer: does the fused posterior know when it is
+    wrong better than either expert does?  ONE pass per data set (net.uncertainty_tables with every expert's own tables):
+    per expert and for the fusion the AUROC of every metric of net.uncertainty_metrics as a detector of that row's own
+    misclassified pixels, with `ood_set` the same as a detector of its pixels (all of them) among the labelled pixels of
+    `testset`, and the mean NLL over the labelled pixels.  Returns {row: {'misclassification': {metric: AUROC},
+    'out_of_distribution': {metric: AUROC} (with ood_set), 'nll': float}}, the fusion under 'fusion'."""
+    from .uncertainty_model import roc_from_histogram
+    inside = net.uncertainty_tables(testset, experts=True)
+    outside = net.uncertainty_tables(ood_set, experts=True, fixed_row=1) if ood_set is not None else None
+    rows = [(name, t, outside['experts'][name] if outside else None) for name, t in inside['experts'].items()]
+    rows.append(('fusion', inside, outside))
+    result = {}
+    for name, t, foreign in rows:
+        counts = int(t['counts'].sum())
+        r = result[name] = {'misclassification': {m: roc_from_histogram(t['hist'][i], t['edges'])[2]
+                                                  for i, m in enumerate(t['metrics'])},
+                            'nll': float(t['nll_sum'].sum() / counts) if counts else float('nan')}
+        if foreign is not None:
+            r['out_of_distribution'] = {m: roc_from_histogram(np.stack([t['hist'][i].sum(0), foreign['hist'][i][1]]), t['edges'])[2]
+                                        for i, m in enumerate(t['metrics'])}
+        if print_results:
+            line = '{:>15}: NLL {:.4f} misclassification AUROC'.format(name, r['nll'])
+            line += ''.join(' {} {:.3f}'.format(m, a) for m, a in r['misclassification'].items())
+            if foreign is not None:
+                line += ' out-of-distribution AUROC' + ''.join(' {} {:.3f}'.format(m, a) for m, a in r['out_of_distribution'].items())
+            print(line)
+    return result
+
+
 def _collect(results, values):
     """Append every leaf of the (nested) dict `values` to the list under the same keys of `results`."""
     for key, value in values.items():

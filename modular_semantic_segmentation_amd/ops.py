@@ -1115,6 +1115,83 @@ def fused_head_multi_confidence(scores, biases, n, hi, wi, num_classes, mode, te
     return maps
 
 
+# ---- uncertainty benchmarks of a posterior (csrc/confidence_stats.hip): the confidence maps counted instead of written
+
+CONFIDENCE_METRICS = ('entropy', 'least_confidence', 'small_margin')    # the order of the kernels' histograms
+
+
+def _confidence_stats_tables(tables, C, device, mantissa_bits, octaves, labels, npix, lead=()):
+    """The accumulators of one confidence_stats launch -- uncertainty_tables(C, device, 3, m, o), with `lead` (E,) in front of
+    every shape for the experts' -- made here when None, else checked; labels int32 of npix values, or None."""
+    if labels is not None:
+        _need(labels, torch.int32, 'labels')
+        if labels.numel() != npix:
+            raise ValueError('labels of shape %s, expected %d values' % (tuple(labels.shape), npix))
+    bins = int(octaves) << int(mantissa_bits)
+    if tables is None:
+        tables = uncertainty_tables(C, device, 3, mantissa_bits, octaves)
+        if lead:
+            tables = {k: t.new_zeros(tuple(lead) + tuple(t.shape)) for k, t in tables.items()}
+    _need(tables['hist'], torch.int64, 'hist')
+    _need(tables['nll'], torch.float64, 'nll')
+    _need(tables['counts'], torch.int64, 'counts')
+    shapes = {'hist': tuple(lead) + (3, 2, bins), 'nll': tuple(lead) + (C,), 'counts': tuple(lead) + (C,)}
+    for k, shape in shapes.items():
+        if tuple(tables[k].shape) != shape:
+            raise ValueError('%s of shape %s, expected %s' % (k, tuple(tables[k].shape), shape))
+    return tables
+
+
+def confidence_stats(values, labels=None, temperature=1.0, kind=0, fixed_row=-1, mantissa_bits=5, octaves=24, tables=None):
+    """The uncertainty benchmarks' statistic of a MATERIALISED map (xv_confidence_stats) -- values and kind as confidence_map
+    takes them -- without writing a map: accumulates into `tables` (uncertainty_tables(C, device, 3, m, o), made here when
+    None) hist[metric][row][bin] of the three CONFIDENCE_METRICS, larger = less certain, each one float32 operation from what
+    confidence_map writes: 'entropy', 'least_confidence' = 1 - confidence, 'small_margin' = 1 - margin.  row = (label of the
+    map != labels) over the pixels with a valid label, or `fixed_row` (0 / 1) for every pixel (labels may then be None); with
+    labels also the NLL sums -- the nll_pixel of calibration_table at this temperature -- and class counts.  Values at or
+    below 2^(1 - octaves) share bin 0: at the default 24 octaves that is the resolution limit of 1 - confidence in float32, so
+    nothing a float32 confidence can tell apart is merged.  Returns the tables."""
+    _need(values, torch.float32, 'values')
+    if values.dim() < 2 or values.numel() == 0 or not 2 <= int(values.shape[-1]) <= 32:
+        raise ValueError('values of shape %s, expected non-empty [n, ..., C] with 2..32 classes' % (tuple(values.shape),))
+    n, C = int(values.shape[0]), int(values.shape[-1])
+    npix = values.numel() // C
+    tables = _confidence_stats_tables(tables, C, values.device, mantissa_bits, octaves, labels, npix)
+    rc = _lib.lib().xv_confidence_stats(_ptr(values), int(kind), n, npix // n, C, float(temperature), _ptr(labels),
+                                       int(mantissa_bits), int(octaves), int(fixed_row), _ptr(tables['hist']),
+                                       _ptr(tables['nll']), _ptr(tables['counts']), _stream())
+    _lib.check(rc, 'xv_confidence_stats')
+    return tables
+
+
+def fused_head_multi_confidence_stats(scores, biases, n, hi, wi, num_classes, mode, labels=None, temperature=1.0, tab=None,
+                                      lognorm=None, logprior=None, fixed_row=-1, mantissa_bits=5, octaves=24, tables=None,
+                                      experts=False, expert_tables=None):
+    """Two to four experts' low-resolution scores (as fused_head_multi_confidence takes them, with its tables for `mode`) ->
+    the tables of confidence_stats for the FUSED posterior in one launch: what confidence_stats counts on the fused score map
+    (Bayes, Dirichlet) or the mean probabilities (kind 1), without that map.  experts=True (or expert_tables given: 'hist'
+    [E, 3, 2, bins], 'nll' and 'counts' [E, C]) also counts every expert's own tables from its interpolated logits, its own
+    label against `labels`.  Returns the tables, with experts (tables, expert_tables)."""
+    mode = FUSED_HEAD_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError('unknown fused head mode %r' % (mode,))
+    scores, biases, E, C = _check_experts(scores, biases, n, hi, wi, num_classes, 'the confidence statistics head')
+    _check_fusion_tables(mode, E, C, tab, lognorm, logprior)
+    device, npix = scores[0].device, n * hi * wi * 64
+    tables = _confidence_stats_tables(tables, C, device, mantissa_bits, octaves, labels, npix)
+    experts = experts or expert_tables is not None
+    if experts:
+        expert_tables = _confidence_stats_tables(expert_tables, C, device, mantissa_bits, octaves, None, npix, lead=(E,))
+    et = expert_tables if experts else {}
+    rc = _lib.lib().xv_fused_head_multi_confidence_stats_fwd(
+        _ptr_array(scores), _ptr_array(biases), E, int(n), int(hi), int(wi), C, int(mode), _ptr(tab), _ptr(lognorm),
+        _ptr(logprior), float(temperature), _ptr(labels), int(mantissa_bits), int(octaves), int(fixed_row),
+        _ptr(tables['hist']), _ptr(tables['nll']), _ptr(tables['counts']), _ptr(et.get('hist')), _ptr(et.get('nll')),
+        _ptr(et.get('counts')), _stream())
+    _lib.check(rc, 'xv_fused_head_multi_confidence_stats_fwd')
+    return (tables, expert_tables) if experts else tables
+
+
 # ---- label-tuple heads (csrc/tuple_lut.hip): the tuple of a pixel's expert labels is t = ((l_0 C + l_1) C + l_2) ..., expert
 # 0 most significant: the row-major index of a [C]*E decision array
 
